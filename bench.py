@@ -11,7 +11,18 @@ Inputs (scene S(200k,800,800,seed 0)) are resident in HBM 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 with the contract fields plus
+Prints ONE JSON line on rank 0 with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, config ...).
+A plain run does only what that line needs: set-up, W warm-up steps, K timed steps, the line.
+
+  --dump-outputs DIR: after the timed steps, what they returned to their caller, the step exactly as a plain run configures it:
+                      loss.npy = the loss of the last timed step, timed_losses.npy = the losses of all K (float32; --workload c2: the
+                      rendered color, radii and allmap of the last view).  The trained parameters are not written: the backward adds
+                      with float atomics, every run in another order, and Adam turns a gradient that is zero to rounding into a full
+                      step of either sign, so two runs with the same arguments end with parameters apart by far more than rounding
+                      (the hyper coordinates by 0.55 relative L2 after 25 steps), while their losses agree to ~1e-5.
+  --full            : also every measurement behind the timed region (the objects below; at N > 1 the `comm` object), added to the line.
+
+With --full the line also holds
   "roofline"        : achieved algorithmic HBM GB/s of the dominant kernel (the backward blend) against the 8 TB/s HBM3E peak.
                       Timed AFTER the headline region, on the scene state the region ended with (snapshot / restore), with
                       device timestamps inside the replayed whole-step graph -- the launch mode of the headline -- and, as a
@@ -27,7 +38,8 @@ Prints ONE JSON line on rank 0 with the contract fields plus
   "drift"           : the scene trains on noise targets while it is timed and its splats grow: ms/step of a second window 100
                       steps after the headline window, and the mean screen radius at both (the headline is the FIRST window);
   "cpu_baseline"    : the CPU port (C oracle rasterizer with OpenMP + PyTorch-CPU deformation/loss/Adam) timed on
-                      this box's host cores for a bounded sample of the same workload (rank 0, N=1 only).
+                      this box's host cores for a bounded sample of the same workload (rank 0, N=1 only);
+  "concurrent_views": two and three views per step in flight at once, in a child process (N=1 only).
 """
 import argparse
 import json
@@ -35,6 +47,8 @@ import os
 import sys
 import threading
 import time
+
+_START = time.time()   # the --full watchdog's budget counts from here
 
 # ROCm 7.2 replays captured graphs through pre-recorded AQL packets by default; with this train step (memset nodes of
 # PyTorch's multi-block reductions and of the rasterizer between kernel nodes) that path intermittently executes a
@@ -228,6 +242,16 @@ def kernel_bytes(kind, P, Pv, R, M, ntiles):
     raise KeyError(kind)
 
 
+def write_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float32 (at most 64 MB in all: the largest, --workload c2, is 28 MB)."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    assert sum(v.nbytes for v in arrays.values()) <= 64_000_000
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+
+
 def forward_only(args, P, H, W, device):
     """configs[1] of BASELINE.json: static canonical surfels rendered forward-only through the operator surface
     (GaussianRasterizer), one view per step, eager launches.  Same JSON contract; the roofline object is the forward blend."""
@@ -256,11 +280,13 @@ def forward_only(args, P, H, W, device):
     _C.profile_reset()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(args.warmup + i)
+        res = step(args.warmup + i)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     prof = _C.profile_read()
     _C.profile_enable(False)
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in zip(("color", "radii", "allmap"), res)})
     ntiles = ((W + 15) // 16) * ((H + 15) // 16)
     n, ms, S = prof["fwd_n"], prof["fwd_ms"], prof["fwd_S"]
     bytes_per = blend_bytes(S / max(n, 1), ntiles, H * W, backward=False)
@@ -455,21 +481,24 @@ _WATCH = {"lock": threading.Lock(), "done": False, "timer": None}
 
 def arm_watchdog(headline, rank, seconds):
     """Everything behind the timed region (communication report and its levers, drift window, roofline legs, twin check, CPU baseline) is a
-    side measurement, and some of it is first-contact code on a multi-GPU box.  If it has not finished after `seconds`, rank 0 prints the
-    HEADLINE line alone (same metric / value / config; the objects that were not measured are absent and `note` says why) and every rank
-    leaves: a collective that never returns must not cost the run its number.  Every rank arms its own timer right behind the barrier that
-    ends the timed region, so they fire together."""
+    side measurement, and some of it is first-contact code on a multi-GPU box.  If the run has not finished `seconds` after the process
+    started, rank 0 prints the HEADLINE line alone (same metric / value / config; the objects that were not measured are absent and `note`
+    says why) and every rank leaves: a collective that never returns must not cost the run its number, and a --full run stays within its
+    time limit.  Every rank arms its own timer right behind the barrier that ends the timed region; the ranks start together, so their
+    timers fire together."""
+    _WATCH["deadline"] = _START + seconds
+
     def bail():
         with _WATCH["lock"]:
             if _WATCH["done"]:
                 return
             _WATCH["done"] = True
             if rank == 0:
-                print(json.dumps(dict(headline, note="measurements behind the timed region did not finish within %d s: headline only" % seconds)), flush=True)
+                print(json.dumps(dict(headline, note="measurements behind the timed region did not finish within %d s of the start: headline only" % seconds)), flush=True)
             sys.stderr.write("bench.py: watchdog after %d s (rank %d)\n" % (seconds, rank))
             sys.stderr.flush()
             os._exit(0)
-    t = threading.Timer(seconds, bail)
+    t = threading.Timer(max(0.0, _WATCH["deadline"] - time.time()), bail)
     t.daemon = True
     t.start()
     _WATCH["timer"] = t
@@ -496,7 +525,14 @@ def main():
     ap.add_argument("--drift-gap", type=int, default=100, help="steps between the headline window and the second (drift) window; 0: skip")
     ap.add_argument("--concurrent-report", type=float, default=None, metavar="MS_HEADLINE",
                     help="internal: print only the concurrent_views object (the main run starts this as a child process, so that nothing in it can cost the headline line)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement behind the timed region (communication report, drift window, roofline legs and twin "
+                         "check, HBM ceiling, concurrent views, CPU baseline); --no-cpu-baseline, --no-roofline-legs and --drift-gap trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps returned (the last step's loss and all K losses; c2: the last view's images) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.concurrent_report is not None:
         torch.cuda.set_device(0)
         P_, H_, W_ = WORKLOADS[args.workload]
@@ -602,21 +638,59 @@ def main():
         for _ in range(tr.GUARD_LAG + 1):   # let the guard see the last steps of the region (it polls with a lag)
             tr.step()
         torch.cuda.synchronize()
-    timed_losses = tr.loss_history(args.steps)
     if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    headline = {
+        "metric": "train views/sec (fwd+bwd), 800x800, 200k surfels" if args.workload == "metric"
+        else "train views/sec (fwd+bwd), %dx%d, %dk surfels" % (W, H, P // 1000),
+        "value": round(args.views_per_rank * world * args.steps / dt, 3), "unit": "views/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": ("%s: synthetic scene S(%d surfels, %dx%d, seed 0), full train step (node deform + surfel "
+                                "raster fwd/bwd + L1/D-SSIM/normal/distortion loss + Adam), 1 view per GPU per step" % (args.workload, P, W, H))
+                   if args.workload != "trained" else
+                   ("trained: DynamicTruth (bobbing sphere + swinging plate, 40k textured surfels) rendered to a D-NeRF-format dataset at %dx%d "
+                    "and fitted for %d iterations from 100k random points with the reference's stages, densification and opacity resets "
+                    "(%d live surfels in %d slots now); the timed step is the same full late-regime train step as 'metric', "
+                    "on the dataset's target views" % (W, H, args.pre_iterations, tr.surfels.num_surfels, tr.P)),
+                   "surfels": P, "image": "%dx%d" % (W, H), "sh_degree": 3, "control_nodes": int(tr.deform.node_num),
+                   "views_per_step": args.views_per_rank * world, "views_per_rank": args.views_per_rank, "views_first_step": views_first_step,
+                   "parallelism": ("dp%d (views sharded; SH gradients reduce-scattered to the rows' owners, updated rows all-gathered; the rest all-reduced)"
+                                   if world > 1 and tr._shard_ok() else "dp%d (views sharded, one flat all-reduce)") % world,
+                   "launch": "whole-step HIP graph replay" if use_graph else "eager",
+                   "neighbour_search": "%s (spatial share of the K-th neighbour distance %.2f)"
+                                       % (tr.deform.knn_refine_mode, getattr(tr.deform, "knn_spatial_share", float("nan")))},
+    }
+    if pre_losses is not None:
+        k = max(len(pre_losses) // 10, 1)
+        headline["config"]["pre_training_loss"] = {"first_tenth_mean": round(sum(pre_losses[:k]) / k, 5), "last_tenth_mean": round(sum(pre_losses[-k:]) / k, 5)}
+        headline["config"]["pre_fit"] = getattr(tr, "pre_fit_mode", "float atomics")
+        # fingerprint of the fitted scene: equal from run to run exactly when the pre-fit is reproducible
+        headline["config"]["pre_fit_fingerprint"] = {"live_surfels": int(tr.surfels.num_surfels), "last_loss": float("%.9g" % pre_losses[-1]),
+                                                     "loss_sum": float("%.12g" % sum(pre_losses))}
+    if args.densify_every:
+        headline["densify"] = {"every": args.densify_every, "calls": len(densify_log), "ms_per_call": [round(m, 3) for m, _ in densify_log],
+                               "cloned_split_pruned": [list(map(int, c)) for _, c in densify_log], "slots": tr.P,
+                               "surfels_after": tr.surfels.num_surfels, "recaptured": tr.P != int(args.slots_factor * P)}
+    if args.dump_outputs and rank == 0:
+        losses = tr.loss_history(args.steps)   # what every timed step returned (the step guard's report ring)
+        write_outputs(args.dump_outputs, {"loss": losses[-1:], "timed_losses": losses})
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything below is measured AFTER the headline and does not change it ---------------------------------------
+    timed_losses = tr.loss_history(args.steps)
     radius_headline = mean_radius(tr)
-    headline = {"metric": "train views/sec (fwd+bwd), 800x800, 200k surfels" if args.workload == "metric" else "train views/sec (fwd+bwd), %dx%d, %dk surfels" % (W, H, P // 1000),
-                "value": round(args.views_per_rank * world * args.steps / dt, 3), "unit": "views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-                "config": {"workload": "%s: synthetic scene S(%d surfels, %dx%d, seed 0), full train step, 1 view per GPU per step" % (args.workload, P, W, H),
-                           "views_per_step": args.views_per_rank * world, "views_first_step": views_first_step, "parallelism": "dp%d" % world}}
     arm_watchdog(headline, rank, int(os.environ.get("DGS_BENCH_WATCHDOG_S", "600")))
     comm = comm_report(tr, args, world, device, dt / args.steps * 1e3, split_choice) if world > 1 else None
 
-    # ---- everything below is measured AFTER the headline and does not change it --------------------------------------------
     # The scene state the headline window ended with is kept: the drift leg trains on, the roofline legs and the twin check
     # are run from this snapshot again.
     snap, it0 = tr._snapshot(), tr.iteration
@@ -790,45 +864,15 @@ def main():
                     "survey_frac": round(b["survey"] / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5), "formula": b["formula"], "R": round(R), "P_visible": round(Pv),
                     "timing": "%s, %d launches" % (label, n)}
 
-        out = {
-            "metric": "train views/sec (fwd+bwd), 800x800, 200k surfels" if args.workload == "metric"
-            else "train views/sec (fwd+bwd), %dx%d, %dk surfels" % (W, H, P // 1000),
-            "value": round(args.views_per_rank * world * args.steps / dt, 3), "unit": "views/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": ("%s: synthetic scene S(%d surfels, %dx%d, seed 0), full train step (node deform + surfel "
-                                    "raster fwd/bwd + L1/D-SSIM/normal/distortion loss + Adam), 1 view per GPU per step" % (args.workload, P, W, H))
-                       if args.workload != "trained" else
-                       ("trained: DynamicTruth (bobbing sphere + swinging plate, 40k textured surfels) rendered to a D-NeRF-format dataset at %dx%d "
-                        "and fitted for %d iterations from 100k random points with the reference's stages, densification and opacity resets "
-                        "(%d live surfels in %d slots now); the timed step is the same full late-regime train step as 'metric', "
-                        "on the dataset's target views" % (W, H, args.pre_iterations, tr.surfels.num_surfels, tr.P)),
-                       "surfels": P, "image": "%dx%d" % (W, H), "sh_degree": 3, "control_nodes": int(tr.deform.node_num),
-                       "views_per_step": args.views_per_rank * world, "views_per_rank": args.views_per_rank, "views_first_step": views_first_step,
-                       "parallelism": ("dp%d (views sharded; SH gradients reduce-scattered to the rows' owners, updated rows all-gathered; the rest all-reduced)"
-                                       if (comm or {}).get("sh_collective", "").startswith("reduce_scatter") else "dp%d (views sharded, one flat all-reduce)") % world,
-                       "launch": "whole-step HIP graph replay" if use_graph else "eager",
-                       "neighbour_search": "%s (spatial share of the K-th neighbour distance %.2f)"
-                                           % (tr.deform.knn_refine_mode, getattr(tr.deform, "knn_spatial_share", float("nan")))},
+        out = dict(headline, **{
             "roofline": roof("bwd"), "roofline_fwd": roof("fwd"),
             "roofline_valu": {"bwd": roof_valu("bwd"), "fwd": roof_valu("fwd")},
             "roofline_kernels": {"preprocess_fwd": roof_kernel("preprocess_fwd", "pre"), "binning": roof_kernel("binning", "bin"),
                                  "surfel_bwd": roof_kernel("surfel_bwd", "sbw")},
             "twin": twin, "drift": drift,
-        }
+        })
         if comm is not None:
             out["comm"] = comm
-        if pre_losses is not None:
-            k = max(len(pre_losses) // 10, 1)
-            out["config"]["pre_training_loss"] = {"first_tenth_mean": round(sum(pre_losses[:k]) / k, 5), "last_tenth_mean": round(sum(pre_losses[-k:]) / k, 5)}
-            out["config"]["pre_fit"] = getattr(tr, "pre_fit_mode", "float atomics")
-            # fingerprint of the fitted scene: equal from run to run exactly when the pre-fit is reproducible
-            out["config"]["pre_fit_fingerprint"] = {"live_surfels": int(tr.surfels.num_surfels), "last_loss": float("%.9g" % pre_losses[-1]),
-                                                    "loss_sum": float("%.12g" % sum(pre_losses))}
-        if args.densify_every:
-            out["densify"] = {"every": args.densify_every, "calls": len(densify_log), "ms_per_call": [round(m, 3) for m, _ in densify_log],
-                              "cloned_split_pruned": [list(map(int, c)) for _, c in densify_log], "slots": tr.P,
-                              "surfels_after": tr.surfels.num_surfels, "recaptured": tr.P != int(args.slots_factor * P)}
         try:
             ceil = measured_hbm_ceiling(device)
             for r in (out["roofline"], out["roofline_fwd"]):
@@ -846,7 +890,8 @@ def main():
             import subprocess
             try:
                 cp = subprocess.run([sys.executable, os.path.abspath(__file__), "--concurrent-report", "%.6f" % (dt / args.steps * 1e3), "--workload", args.workload,
-                                     "--steps", str(args.steps), "--warmup", str(args.warmup)], capture_output=True, text=True, timeout=600)
+                                     "--steps", str(args.steps), "--warmup", str(args.warmup)], capture_output=True, text=True,
+                                    timeout=max(1.0, min(600.0, _WATCH["deadline"] - time.time() - 10.0)))   # killed before the watchdog fires
                 lines = [l for l in cp.stdout.splitlines() if l.startswith("{")]
                 out["concurrent_views"] = json.loads(lines[-1]) if cp.returncode == 0 and lines else {"error": "child exited with %d: %s" % (cp.returncode, cp.stderr[-300:])}
             except Exception as ex:

@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -29,7 +30,7 @@ def test_bench_two_ranks_prints_one_valid_line():
         env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    DGS_DIST_BACKEND="gloo")
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "2",
-                                       "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+                                       "--full", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=600) for p in procs]
     for p, (so, se) in zip(procs, outs):
         assert p.returncode == 0, se[-3000:]
@@ -50,6 +51,30 @@ def test_bench_two_ranks_prints_one_valid_line():
     assert c["split3"]["chosen"] in ("two", "three") and c["split3"]["ms_per_step_two_pieces"] > 0 and c["split3"]["ms_per_step_three_pieces"] > 0
 
 
+def test_bench_two_ranks_plain_line_and_dump(tmp_path):
+    """The plain launch (no --full) at N = 2: the headline line from rank 0 only, nothing measured behind the timed region, rank 0 alone
+    writes the dump (the losses of its K timed steps), and every rank leaves through the closing barrier with status 0."""
+    world, port = 2, _free_port()
+    procs = []
+    for rank in range(world):
+        env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
+                   DGS_DIST_BACKEND="gloo")
+        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "2",
+                                       "--dump-outputs", str(tmp_path)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+    outs = [p.communicate(timeout=600) for p in procs]
+    for p, (so, se) in zip(procs, outs):
+        assert p.returncode == 0, se[-3000:]
+    lines = [l for l in outs[0][0].splitlines() if l.startswith("{")]
+    assert len(lines) == 1 and not [l for l in outs[1][0].splitlines() if l.startswith("{")], "exactly one JSON line, from rank 0"
+    r = json.loads(lines[0])
+    assert r["n_gpus"] == 2 and r["steps"] == 4 and r["warmup"] == 2 and r["config"]["parallelism"].startswith("dp2")
+    assert r["value"] > 0 and abs(r["value"] - 2 * 1e3 / r["ms_per_step"]) <= 1e-2 * r["value"]
+    assert not {"comm", "roofline", "twin", "drift", "cpu_baseline", "note"} & set(r)
+    assert sorted(os.listdir(tmp_path)) == ["loss.npy", "timed_losses.npy"]
+    loss, tl = np.load(tmp_path / "loss.npy"), np.load(tmp_path / "timed_losses.npy")
+    assert tl.shape == (4,) and np.isfinite(tl).all() and loss[0] == tl[-1]
+
+
 def test_bench_two_ranks_two_views_per_rank():
     """The same launch with --views-per-rank 2 (Trainer.views_per_rank: two views per rank added before the one exchange of a step):
     four views per step, the rate counts views, one exchange per step (no split: the SH slice is part of `rest`), and the
@@ -60,7 +85,7 @@ def test_bench_two_ranks_two_views_per_rank():
         env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    DGS_DIST_BACKEND="gloo")
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "2",
-                                       "--no-cpu-baseline", "--no-roofline-legs", "--views-per-rank", "2"], env=env, stdout=subprocess.PIPE,
+                                       "--full", "--no-cpu-baseline", "--no-roofline-legs", "--views-per-rank", "2"], env=env, stdout=subprocess.PIPE,
                                       stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=600) for p in procs]
     for p, (so, se) in zip(procs, outs):
@@ -84,7 +109,7 @@ def test_bench_eight_ranks_dry_run():
     for rank in range(world):
         env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    DGS_DIST_BACKEND="gloo", DGS_LEVER_CONCURRENT="1")   # (the concurrent-lanes lever is opt-in at N > 1: covered here)
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "2", "--drift-gap", "10"],
+        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "2", "--drift-gap", "10", "--full"],
                                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=1500) for p in procs]
     for p, (so, se) in zip(procs, outs):
@@ -113,7 +138,7 @@ def test_bench_watchdog_prints_the_headline_alone():
     env = dict(os.environ, DGS_BENCH_WATCHDOG_S="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "4", "--warmup", "2"], env=env,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "4", "--warmup", "2", "--full"], env=env,
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

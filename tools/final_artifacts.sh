@@ -29,9 +29,9 @@ if [ "$1" = "pmc" ]; then
   bash tools/pmc_kernels.sh r06_c5 "dgs::" c5 2>&1 | tail -12
   exit 0
 fi
-python bench.py > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench.err; tail -c 200 $O/${TAG}_bench_line.json; echo
-for w in c2 c3 c4 c5; do timeout 300 python bench.py --workload $w --no-cpu-baseline > $O/${TAG}_bench_line_$w.json 2>/dev/null; done
-for i in "" _2 _3; do timeout 400 python bench.py --workload trained --no-cpu-baseline > $O/${TAG}_bench_line_trained$i.json 2>/dev/null; done
+python bench.py --full > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench.err; tail -c 200 $O/${TAG}_bench_line.json; echo
+for w in c2 c3 c4 c5; do timeout 300 python bench.py --full --workload $w --no-cpu-baseline > $O/${TAG}_bench_line_$w.json 2>/dev/null; done
+for i in "" _2 _3; do timeout 400 python bench.py --full --workload trained --no-cpu-baseline > $O/${TAG}_bench_line_trained$i.json 2>/dev/null; done
 cd /tmp && export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof -o k -- python $R/bench.py --no-cpu-baseline --no-roofline-legs --steps 10 > $O/${TAG}_prof.log 2>&1
 F=$(ls $O/${TAG}_prof/*kernel_stats.csv 2>/dev/null | head -1); T=$(ls $O/${TAG}_prof/*kernel_trace.csv 2>/dev/null | head -1)

@@ -8,7 +8,7 @@ mkdir -p $O
 cd $R
 echo "== pytest -m gpu"; timeout 600 python -m pytest tests -m gpu -x -q 2>&1 | tail -3
 echo "== smoke"; timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
-echo "== bench (with cpu baseline)"; timeout 400 python bench.py > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench.err; tail -c 300 $O/${TAG}_bench_line.json
+echo "== bench (with cpu baseline)"; timeout 400 python bench.py --full > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench.err; tail -c 300 $O/${TAG}_bench_line.json
 cd /tmp && export TMPDIR=/tmp
 echo "== rocprofv3 kernel trace of the bench command"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof -o k -- python $R/bench.py --no-cpu-baseline --no-roofline-legs --steps 10 > $O/${TAG}_prof.log 2>&1
