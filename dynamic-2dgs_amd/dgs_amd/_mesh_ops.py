@@ -1,0 +1,131 @@
+"""ctypes binding of libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion and marching tetrahedra for gfx950, used by
+dgs_amd.mesh when the volume lives on a HIP device.  CPU tensors use the PyTorch / NumPy statement in dgs_amd.mesh."""
+import ctypes
+import os
+
+import torch
+
+from . import _ops
+
+_CSRC = _ops._CSRC
+LIB_PATH = os.path.join(_CSRC, "libdgs_mesh_ops.so")
+# -ffp-contract=off: the fuser's accept / reject decisions sit on thresholds; with every operation rounded on its own the kernel
+# and the PyTorch statement of the same arithmetic take the same side of every one of them
+HIPCC_FLAGS = list(_ops.HIPCC_FLAGS) + ["-ffp-contract=off"]
+_lib = None
+_EXPORTS = ("dgs_mesh_ops_abi_version", "dgs_mesh_ops_last_error", "dgs_tsdf_integrate", "dgs_mt_classify", "dgs_mt_emit")
+
+
+def _deps():
+    hdr = os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dgs_mesh_ops.h")
+    return [os.path.join(_CSRC, "mesh_ops.hip"), hdr]
+
+
+def source_hash():
+    import _dgs_build
+    return _dgs_build.source_hash(_deps(), HIPCC_FLAGS)
+
+
+def build(force=False, verbose=False):
+    """hipcc, in-tree; rebuilt whenever the hash of sources + flags differs from the one recorded with the binary."""
+    import _dgs_build
+    cmd = ["hipcc"] + HIPCC_FLAGS + [os.path.join(_CSRC, "mesh_ops.hip"), "-o", LIB_PATH]
+    return _dgs_build.build(LIB_PATH, cmd, _deps(), HIPCC_FLAGS, _CSRC, force=force, verbose=verbose)[0]
+
+
+def exported_symbols():
+    return _EXPORTS
+
+
+def load():
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise RuntimeError("%s not found; build it with __graft_entry__.build()" % LIB_PATH)
+        from diff_surfel_rasterization._C import _refuse_stale
+        _refuse_stale(LIB_PATH, source_hash, build)   # never run a binary built from other sources than the tree's
+        lib = ctypes.CDLL(LIB_PATH)
+        vp, ci, cf, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_longlong
+        lib.dgs_mesh_ops_abi_version.restype = ci
+        lib.dgs_mesh_ops_last_error.restype = ctypes.c_char_p
+        lib.dgs_tsdf_integrate.restype = ci
+        lib.dgs_tsdf_integrate.argtypes = [ci, ci, ci, cf, cf, cf, cf, ci, ci, ci, vp, vp, vp, cf, cf, cf, ci, vp, vp, vp, vp]
+        lib.dgs_mt_classify.restype = ci
+        lib.dgs_mt_classify.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp]
+        lib.dgs_mt_emit.restype = ci
+        lib.dgs_mt_emit.argtypes = [ci, ci, ci, cf, cf, cf, cf, vp, vp, ll, vp, vp, vp, ll, vp, vp, vp, vp, vp, vp, vp]
+        if lib.dgs_mesh_ops_abi_version() != 1:
+            raise RuntimeError("libdgs_mesh_ops.so ABI version mismatch (want 1, library says %d): rebuild it" % lib.dgs_mesh_ops_abi_version())
+        _lib = lib
+    return _lib
+
+
+def _check(lib, rc, what):
+    if rc < 0:
+        raise RuntimeError("%s failed (%d): %s" % (what, rc, lib.dgs_mesh_ops_last_error().decode()))
+
+
+def _stream(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _f32(t, what):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+        raise RuntimeError("%s: a contiguous fp32 HIP tensor is expected" % what)
+    return t
+
+
+def tsdf_integrate(dims, origin, voxel, depth, rgb, proj, trunc, depth_trunc, prior_weight, accumulate, tsdf, weight, color):
+    """dgs_tsdf_integrate on the volume tensors tsdf / weight [Nx,Ny,Nz] and color [Nx,Ny,Nz,3] (in place)."""
+    lib = load()
+    dev = tsdf.device
+    V, H, W = depth.shape
+    n = dims[0] * dims[1] * dims[2]
+    if rgb.shape != (V, 3, H, W) or proj.shape != (V, 16) or tsdf.numel() != n or weight.numel() != n or color.numel() != 3 * n:
+        raise RuntimeError("tsdf_integrate: depth [V,H,W], rgb [V,3,H,W], proj [V,16] and a volume of the given dims are expected")
+    for t, what in ((depth, "depth"), (rgb, "rgb"), (proj, "proj"), (tsdf, "tsdf"), (weight, "weight"), (color, "color")):
+        _f32(t, what)
+        if t.device != dev:
+            raise RuntimeError("tsdf_integrate: %s lives on another device than the volume" % what)
+    with torch.cuda.device(dev):
+        rc = lib.dgs_tsdf_integrate(dims[0], dims[1], dims[2], origin[0], origin[1], origin[2], voxel, V, H, W, depth.data_ptr(), rgb.data_ptr(),
+                                    proj.data_ptr(), trunc, depth_trunc, prior_weight, 1 if accumulate else 0, tsdf.data_ptr(),
+                                    weight.data_ptr(), color.data_ptr(), _stream(dev))
+    _check(lib, rc, "dgs_tsdf_integrate")
+
+
+def marching_tetrahedra(dims, origin, voxel, tsdf, weight, color=None):
+    """(vertices [Nv,3] f32, faces [Nf,3] int32, colors [Nv,3] f32 or None) of the volume, in the order of include/dgs_mesh_ops.h.
+    PyTorch does the plumbing between the two passes: two prefix sums, the lists of active cells and of vertex-carrying grid
+    points, and the one host read of the two totals that sizes the outputs."""
+    lib = load()
+    dev = tsdf.device
+    Nx, Ny, Nz = dims
+    n = Nx * Ny * Nz
+    _f32(tsdf, "tsdf"), _f32(weight, "weight")
+    if color is not None:
+        _f32(color, "color")
+    cell_tris = torch.empty(n, dtype=torch.int32, device=dev)
+    point_verts = torch.empty(n, dtype=torch.int32, device=dev)
+    point_mask = torch.empty(n, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib, lib.dgs_mt_classify(Nx, Ny, Nz, tsdf.data_ptr(), weight.data_ptr(), cell_tris.data_ptr(), point_verts.data_ptr(),
+                                        point_mask.data_ptr(), _stream(dev)), "dgs_mt_classify")
+    tri_incl = torch.cumsum(cell_tris, 0, dtype=torch.int64)
+    vert_incl = torch.cumsum(point_verts, 0, dtype=torch.int64)
+    n_tris, n_verts = (int(x) for x in torch.stack((tri_incl[-1], vert_incl[-1])).tolist())
+    if n_verts >= 2 ** 31 or n_tris >= 2 ** 31:
+        raise RuntimeError("marching_tetrahedra: %d vertices / %d triangles do not fit the int32 face indices" % (n_verts, n_tris))
+    vertices = torch.empty((n_verts, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((n_tris, 3), dtype=torch.int32, device=dev)
+    colors = torch.empty((n_verts, 3), dtype=torch.float32, device=dev) if color is not None else None
+    if n_tris:
+        cells = torch.nonzero(cell_tris).reshape(-1)
+        points = torch.nonzero(point_mask).reshape(-1)
+        with torch.cuda.device(dev):
+            rc = lib.dgs_mt_emit(Nx, Ny, Nz, origin[0], origin[1], origin[2], voxel, tsdf.data_ptr(), None if color is None else color.data_ptr(),
+                                 cells.numel(), cells.data_ptr(), cell_tris.data_ptr(), tri_incl.data_ptr(), points.numel(), points.data_ptr(),
+                                 point_mask.data_ptr(), vert_incl.data_ptr(), vertices.data_ptr(), None if colors is None else colors.data_ptr(),
+                                 faces.data_ptr(), _stream(dev))
+        _check(lib, rc, "dgs_mt_emit")
+    return vertices, faces, colors

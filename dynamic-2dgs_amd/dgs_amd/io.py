@@ -87,6 +87,79 @@ def read_ply(path):
         return raw.astype([(n, t) for n, t in el["props"]])
 
 
+def write_mesh_ply(path, vertices, faces, colors=None):
+    """A triangle mesh as binary little-endian PLY: `element vertex` (float x y z, then uchar red green blue when `colors` [Nv,3] in
+    [0, 1] is given) followed by `element face` with `property list uchar int vertex_indices` -- the layout trimesh, open3d and the
+    reference's read_gt_mesh.py read (render_mesh.py:218 writes it through open3d)."""
+    to_np = lambda x: x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    v, f = to_np(vertices).reshape(-1, 3), to_np(faces).reshape(-1, 3)
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError("write_mesh_ply: face index out of range")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    head = ["ply", "format binary_little_endian 1.0", "element vertex %d" % v.shape[0], "property float x", "property float y", "property float z"]
+    if colors is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        head += ["property uchar red", "property uchar green", "property uchar blue"]
+    head += ["element face %d" % f.shape[0], "property list uchar int vertex_indices", "end_header"]
+    vert = np.empty(v.shape[0], dtype=fields)
+    for i, n in enumerate("xyz"):
+        vert[n] = v[:, i]
+    if colors is not None:
+        c = np.round(np.clip(to_np(colors).reshape(-1, 3), 0.0, 1.0) * 255.0).astype(np.uint8)
+        for i, n in enumerate(("red", "green", "blue")):
+            vert[n] = c[:, i]
+    face = np.empty(f.shape[0], dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    face["n"] = 3
+    face["v"] = f
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(head) + "\n").encode("ascii"))
+        fh.write(vert.tobytes())
+        fh.write(face.tobytes())
+
+
+def read_mesh_ply(path):
+    """(vertices [Nv,3] float32, faces [Nf,3] int32, colors [Nv,3] float32 in [0, 1] or None) of a binary little-endian triangle
+    mesh PLY: a `vertex` element of scalar properties followed by a `face` element that is one list of three indices per face."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError("%s: not a PLY file" % path)
+        elements, cur, fmt = [], None, None
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError("%s: truncated PLY header" % path)
+            tok = line.decode("ascii").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                cur = {"name": tok[1], "count": int(tok[2]), "props": []}
+                elements.append(cur)
+            elif tok[0] == "property":
+                cur["props"].append(tuple(tok[1:]))
+            elif tok[0] == "end_header":
+                break
+        if fmt != "binary_little_endian" or [e["name"] for e in elements[:2]] != ["vertex", "face"]:
+            raise ValueError("%s: a binary little-endian PLY with a vertex and a face element is expected" % path)
+        ve, fe = elements[0], elements[1]
+        vdt = np.dtype([(p[1], "<" + _PLY_TYPES[p[0]]) for p in ve["props"]])
+        vert = np.frombuffer(f.read(vdt.itemsize * ve["count"]), dtype=vdt, count=ve["count"])
+        if len(fe["props"]) != 1 or fe["props"][0][0] != "list":
+            raise ValueError("%s: the face element must be one index list" % path)
+        _, cnt_t, idx_t, _ = fe["props"][0]
+        fdt = np.dtype([("n", "<" + _PLY_TYPES[cnt_t]), ("v", "<" + _PLY_TYPES[idx_t], (3,))])
+        face = np.frombuffer(f.read(fdt.itemsize * fe["count"]), dtype=fdt, count=fe["count"])
+        if face.shape[0] != fe["count"] or vert.shape[0] != ve["count"] or (face.size and not (face["n"] == 3).all()):
+            raise ValueError("%s: truncated, or not a triangle mesh" % path)
+    vertices = np.stack([vert["x"], vert["y"], vert["z"]], -1).astype(np.float32)
+    colors = None
+    if all(n in vert.dtype.names for n in ("red", "green", "blue")):
+        colors = np.stack([vert["red"], vert["green"], vert["blue"]], -1).astype(np.float32) / 255.0
+    return vertices, face["v"].astype(np.int32), colors
+
+
 # ---- surfel checkpoint --------------------------------------------------------------------------------------------------
 def surfel_attribute_names(n_dc=3, n_rest=45, n_scale=2, n_rot=4, fea_dim=8):
     """construct_list_of_attributes (gaussian_model.py:229-243)."""

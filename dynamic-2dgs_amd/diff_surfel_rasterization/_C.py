@@ -67,7 +67,7 @@ def _refuse_stale(lib_path, hash_fn, build_fn):
     """A binary built from other sources than the ones in the tree must never be what the tests or the bench measure: if the
     hash recorded next to it differs from the hash of the current sources + flags, rebuild; if that is impossible, fail."""
     import _dgs_build
-    if os.path.basename(lib_path) not in (LIB_NAME, "libdgs_train_ops.so") or os.path.dirname(os.path.abspath(lib_path)) != os.path.abspath(_CSRC):
+    if os.path.basename(lib_path) not in (LIB_NAME, "libdgs_train_ops.so", "libdgs_mesh_ops.so") or os.path.dirname(os.path.abspath(lib_path)) != os.path.abspath(_CSRC):
         return   # DGS_SURFEL_LIB override: an explicit A/B or twin build (its own flags), the caller's responsibility
     have, want = _dgs_build.recorded_hash(lib_path), hash_fn()
     if have == want:

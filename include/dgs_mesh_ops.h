@@ -1,0 +1,80 @@
+/*
+ * dgs_mesh_ops.h -- C ABI of the mesh-extraction kernels: depth-map fusion into a truncated signed distance volume and
+ * marching tetrahedra over it.  They replace the PyTorch / open3d path of the reference's render_mesh.py:
+ *
+ *   dgs_tsdf_integrate          <-  utils/mesh_utils.py:218-266  compute_sdf_perframe + compute_unbounded_tsdf (inv_contraction=None)
+ *   dgs_mt_classify / _emit     <-  utils/mesh_utils.py:158-199 / :268-271  volume.extract_triangle_mesh() / marching_cubes_with_contraction
+ *
+ * All pointers are device pointers, fp32 contiguous unless noted; every call is asynchronous on `stream`.
+ * Return value: 0 or a negative status, message through dgs_mesh_ops_last_error().
+ *
+ * THE GRID.  Dense, dims (Nx, Ny, Nz); grid point (i, j, k) sits at origin + voxel * (i, j, k) (one multiply, one add, fp32) and has
+ * the 64-bit linear index (i * Ny + j) * Nz + k -- the C order of a [Nx, Ny, Nz] tensor, z fastest.
+ */
+#ifndef DGS_MESH_OPS_H
+#define DGS_MESH_OPS_H
+
+#include <stddef.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define DGS_MESH_OPS_ABI_VERSION 1
+
+int dgs_mesh_ops_abi_version(void);
+const char* dgs_mesh_ops_last_error(void);
+
+/* Fuse V views into the volume: ONE launch, the loop over the views inside the kernel, (tsdf, weight, colour) of a voxel in registers
+ * and one store per voxel at the end.
+ *   depth [V,H,W]   view-space z per pixel, 0 = nothing there;   rgb [V,3,H,W];   H, W >= 2
+ *   proj  [V,16]    each camera's full_proj_transform as stored (row-vector convention: hom = [p, 1] @ proj)
+ *   tsdf, weight [Nx*Ny*Nz];   color [Nx*Ny*Nz, 3] (three fp32 per voxel, not packed)
+ *   accumulate = 0: the state starts at weight = prior_weight, tsdf = (prior_weight > 0 ? 1 : 0), colour 0 and is overwritten;
+ *   accumulate = 1: the three arrays are read first, so views may be fed in chunks (bit-identical to one call).
+ * Per voxel p and view, in this order, every operation a separately rounded fp32 one (the library is compiled with
+ * -ffp-contract=off; dgs_amd/mesh.py states the same arithmetic in PyTorch):
+ *   1. hom_c = p.x * proj[0][c] + ((p.y * proj[1][c] + p.z * proj[2][c]) + proj[3][c]) for c in {0, 1, 3};  z = hom_3;
+ *      ndc = hom.xy / z;  reject unless z > 0 and -1 < ndc.x, ndc.y < 1
+ *   2. u = ((ndc.x + 1) * W - 1) / 2, v likewise;  u0 = clamp(floor(u), 0, W - 2), fraction clamp(u - u0, 0, 1);  four depth taps,
+ *      d = (d00 * (1 - fu) + d01 * fu) * (1 - fv) + (d10 * (1 - fu) + d11 * fu) * fv
+ *   3. reject unless every tap satisfies 0 < tap <= depth_trunc
+ *   4. sdf = d - z;  reject unless sdf > -trunc;  s = clamp(sdf / trunc, -1, 1)
+ *   5. tsdf <- (tsdf * w + s) / (w + 1);  if sdf < trunc: colour <- (colour * w + bilinear rgb) / (w + 1);  w <- w + 1
+ * Departures from the reference's torch fuser: (1) weights start at 0, not at 1 with a prior tsdf of 1 (prior_weight = 1 gives the
+ * reference's start); (2) the pixel convention is the rasterizer's (pixel i's centre at ndc (2 i + 1) / W - 1), not
+ * grid_sample(align_corners=True); (3) step 3 -- no interpolation across a silhouette into depth 0; (4) the colour is only
+ * sampled where |sdf| < trunc (a view that sees the voxel as free space leaves its colour as it is).
+ * No tap address can leave the view's image for any camera: taps are only formed from u0 in [0, W - 2], v0 in [0, H - 2]. */
+int dgs_tsdf_integrate(int Nx, int Ny, int Nz, float origin_x, float origin_y, float origin_z, float voxel, int V, int H, int W,
+                       const float* depth, const float* rgb, const float* proj, float trunc, float depth_trunc, float prior_weight,
+                       int accumulate, float* tsdf, float* weight, float* color, void* stream);
+
+/* Marching tetrahedra, pass 1.  Cell (i, j, k) (i < Nx-1 ...) has corner c at (i + (c & 1), j + (c >> 1 & 1), k + (c >> 2 & 1)) and is
+ * cut into the six Kuhn tetrahedra {0, 1<<a, 1<<a | 1<<b, 7} of the permutations (a, b, c) of (0, 1, 2) in lexicographic order.
+ * A cell is ACTIVE iff all 8 corners have weight > 0 and the corner signs (tsdf < 0) differ.
+ *   cell_tris   [Nx*Ny*Nz] int32: triangles of the cell that starts at this grid point (0: inactive, or no cell starts here)
+ *   point_mask  [Nx*Ny*Nz] uint8: bit (d - 1) set iff the edge from this grid point g to g + ((d & 1), (d >> 1 & 1), (d >> 2 & 1)),
+ *               d in 1..7, carries a mesh vertex: its ends differ in sign and at least one active cell contains it
+ *   point_verts [Nx*Ny*Nz] int32: number of set bits
+ * A mesh vertex has the key (linear index of g) * 7 + (d - 1); its id is the rank of its key, the caller's inclusive prefix sums of
+ * the two count arrays turn the counts into offsets. */
+int dgs_mt_classify(int Nx, int Ny, int Nz, const float* tsdf, const float* weight, int* cell_tris, int* point_verts,
+                    unsigned char* point_mask, void* stream);
+
+/* Marching tetrahedra, pass 2.  cells [n_cells] / points [n_points]: ascending linear indices (int64) of the grid points with
+ * cell_tris > 0 / point_mask != 0; tri_incl, vert_incl [Nx*Ny*Nz] int64: INCLUSIVE prefix sums of cell_tris and point_verts.
+ *   vertices [Nv,3], vertex_colors [Nv,3] (color may be NULL, then vertex_colors is not written): position pa + t * (pb - pa) with
+ *     t = fa / (fa - fb), a the edge's lower end; colour with the same t.  Ascending by key.
+ *   faces [Nf,3] int32, ascending by (cell, tetrahedron, triangle within the tetrahedron).  One or three negative corners: the apex
+ *     joined to the other three corners in ascending order; two negative corners a < b, non-negative c < d: the quad (a,c), (a,d),
+ *     (b,d), (b,c) split along its first and third vertex.  Then wound so that the normal points from negative to positive tsdf. */
+int dgs_mt_emit(int Nx, int Ny, int Nz, float origin_x, float origin_y, float origin_z, float voxel, const float* tsdf,
+                const float* color, long long n_cells, const long long* cells, const int* cell_tris, const long long* tri_incl,
+                long long n_points, const long long* points, const unsigned char* point_mask, const long long* vert_incl,
+                float* vertices, float* vertex_colors, int* faces, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
