@@ -1,0 +1,467 @@
+"""The captured step: HIP-graph capture of the training step in its shapes (one view, k views added, the data-parallel split step,
+concurrent lanes), what a replay needs in front of it (the device-side view selection), and the switches that are baked into a
+capture and therefore re-capture it (regime, SH degree, deterministic mode).
+
+Mixin of dgs_amd.train.Trainer."""
+import os
+
+import torch
+
+from .render import camera_rays
+
+
+class StaticCamera:
+    """Camera whose tensors are views of ONE fixed 64-float device row: the captured step reads them, `load` refills the
+    row with a single 256-byte copy per view (nine separate copies -- two of them 7.7 MB: the ray table and the target
+    image -- cost 56 us of a 1.4 ms step).  The row also carries two POINTERS (`slots`: target image, ray table) that the
+    loss kernels dereference at run time, so the big per-view arrays stay where they are.
+    row layout (floats): world_view 0:16 | full_proj 16:32 | camera_center 32:35 | fid 35 | rays_o 36:39 | slots 40:44 (2 x int64)"""
+    ROW = 64
+
+    def __init__(self, cam, device, rays_d, target):
+        self.image_height, self.image_width = cam.image_height, cam.image_width
+        self.FoVx, self.FoVy = cam.FoVx, cam.FoVy
+        self.row = torch.zeros(self.ROW, dtype=torch.float32, device=device)
+        self.world_view_transform = self.row[0:16].view(4, 4)
+        self.full_proj_transform = self.row[16:32].view(4, 4)
+        self.camera_center = self.row[32:35]
+        self.fid = self.row[35:36]
+        self.rays_o = self.row[36:39]
+        self.slots = self.row[40:44].view(torch.int64)
+        self.rays_d = rays_d      # placeholders of the right shape: the kernels follow `slots`
+        self.target = target
+
+    @staticmethod
+    def pack(cam, rays_d, rays_o, target):
+        """One table row (CPU float32 tensor) for this view; the tensors it points to must stay alive."""
+        import numpy as np
+        row = np.zeros(StaticCamera.ROW, np.float32)
+        row[0:16] = cam.world_view_transform.detach().cpu().numpy().reshape(-1)
+        row[16:32] = cam.full_proj_transform.detach().cpu().numpy().reshape(-1)
+        row[32:35] = cam.camera_center.detach().cpu().numpy().reshape(-1)
+        row[35] = float(cam.fid.detach().cpu().reshape(-1)[0])
+        row[36:39] = rays_o.detach().cpu().numpy().reshape(-1)
+        row.view(np.int64)[20:22] = [target.data_ptr(), rays_d.data_ptr()]
+        return torch.from_numpy(row)
+
+    def load(self, table_row):
+        self.row.copy_(table_row, non_blocking=True)
+
+
+class CaptureMixin:
+    _g0 = _g1 = _g1b = _g1c = None    # captured graphs of a one-view step: head (sharded SH) | half a or the whole step | half b (b1) | b2 (third split)
+    _g2 = _g2a = _g2b = None          # data parallel: the update graphs (everything else | SH | third split's per-surfel parameters)
+    _gk = None                        # k views added: [first, middle, last] view's graph
+    _vctr_host = 0                    # host mirror of the device's view counter
+    _deterministic = False            # set_deterministic
+    _det_saved = (0, 1)               # rasterizer options 7, 9 as set_deterministic(True) found them
+
+    def _ctx_option(self, key, value):
+        """dgs_set_option on the library context this trainer's renders run in: its lane's, or the device's default one."""
+        from diff_surfel_rasterization import _C
+        if self._lane is not None:
+            self._lane.context.set_option(key, value)
+        else:
+            _C.set_option(key, value, device=self.surfels.get_xyz.device)
+
+    def _ctx_overflow_flag(self, flag):
+        from diff_surfel_rasterization import _C
+        if self._lane is not None:
+            self._lane.context.set_overflow_flag(flag)
+        else:
+            _C.set_overflow_flag(flag)
+
+    # ---- whole-step HIP graph ------------------------------------------------------------------------------------
+    def enable_graph(self, capacity, validate=True):
+        """Capture deform -> render -> loss -> backward (-> Adam when single-GPU) into HIP graphs and replay them per
+        step: the step is ~400 small launches and otherwise bound by the host, not the GPU.  Needs the rasterizer's
+        capacity mode (`capacity` list entries; no device->host read inside the step).  Per view, one 256-byte row (camera,
+        time, pointers of target image and ray table) is copied into a static buffer before each replay.  Under data
+        parallelism the all-reduce stays outside the graphs.
+        One function per shape of the capture: _capture_lanes (concurrent views), _capture_k_views, _capture_split, _capture_single,
+        and _capture_updates for the data-parallel update graphs."""
+        assert self.rasterizer_cls is None and self.opt_deform is None, "graph capture is for the HIP operator with the flat Adam kernel"
+        assert not self._mask_terms(), "a ground-truth-mask term is active (random backgrounds, a second render): capture the step once it is not"
+        if self.arap:
+            from .arap import lambda_arap
+            assert lambda_arap(self.iteration + 1) == 0, "the ARAP regulariser is still active: capture the step after iteration 20000"
+        # (Rounds 1-4 refused to capture unless DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 was in the environment: ROCm 7.2's default replay path --
+        # pre-recorded AQL packets -- ran a memset node of the step out of order now and then.  The step has had no memset / fill node
+        # since round 4, and tools/diag/graph_knob_probe.py found 2000 replays of the metric step clean with the knob at either value
+        # (round 5: twin 8.6e-6 / 1.2e-5, the same two guard-recovery steps in both series), so the requirement is gone; bench.py and
+        # the tests still default the knob to 0, the configuration every committed number was measured in.)
+        dev = self.surfels.get_xyz.device
+        self._wait_gather()        # (sharded data-parallel step: the SH rows of the last step's update may still be on the wire)
+        if self._overlap_was is not None:   # a capture of concurrent lanes ran this module without its inner forks (_capture_lanes)
+            self.deform.overlap_streams, self._overlap_was = self._overlap_was, None
+        if self._graph and self._flush_guard():   # a live capture is being replaced: settle what its last steps reported first
+            return                 # the recovery re-captured already (with a larger capacity / without the promise)
+        if hasattr(self.deform, "pick_knn_refine"):
+            self.deform.pick_knn_refine(self.surfels)   # the neighbour-search kernel that fits the scene now is baked into the capture
+        self._capacity = int(capacity)
+        self._ctx_option(2, int(capacity))   # capacity mode (the context of THIS trainer's device -- or lane --, whatever the caller's current device is)
+        # promise of the longest tile list (dgs_set_option key 6): one sort launch instead of three.  A frame that breaks it
+        # counts as an overflow: at capture time (below) and in the step guard the promise is withdrawn first, the capacity
+        # doubled only if that was not the reason
+        if self._list_hint is None:
+            self._list_hint = 2048
+        self._ctx_option(6, self._list_hint)
+        if self._oflag is not None:
+            self._ctx_overflow_flag(self._oflag)   # the captured launches keep THIS trainer's flag
+            if not self._in_recovery:
+                self._oflag.zero_()             # read_overflow below reports overflows of THIS capture only
+        self._prepare_views(dev)
+        if self._concurrent():
+            self._capture_lanes(dev)
+            self._graph = True
+            return self._validate_capture(capacity, validate, dev)
+        s = self._warm_up()
+        self._g1 = torch.cuda.CUDAGraph()
+        self._g1b = self._g1c = self._g0 = self._glanes = self._gk = None
+        # thread-local capture mode: with a process group alive, the collective library's watchdog thread polls events while
+        # this thread captures; under the default ("global") mode such a call from ANOTHER thread invalidates the capture
+        # and the watchdog dies with the error (seen once in three runs on ROCm 7 / RCCL 2.26)
+        # capture ON the warm-up stream: per-stream persistent buffers created by the warm-up steps (the coherent skinning table of
+        # _ops._FusedDeform.backward) are found again instead of being allocated -- and zero-filled on every replay -- inside the graph
+        mode = {"capture_error_mode": "thread_local", "stream": s}
+        self._split = self._split_ok()
+        if self.views_per_rank > 1:
+            self._capture_k_views(mode)
+        elif self._split:
+            self._capture_split(mode)
+        else:
+            self._capture_single(mode)
+        self._capture_updates(mode)
+        self._graph = True
+        if os.environ.get("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "") != "0" and not self._store_now:
+            #  rounds 1-4 refused to capture without the knob; the requirement went when the DEFAULT step lost its last
+            # memset node -- this captured step still has one (the bucket's fill: gradients are not stored in place here), and ROCm 7.2's
+            # packet-replay path ran such nodes out of order now and then (an L1 term of exactly 0, or 1e18 gradients)
+            import warnings
+            warnings.warn("captured step contains fill nodes and DEBUG_CLR_GRAPH_PACKET_CAPTURE is not 0: ROCm 7.2 has replayed such nodes out of order; "
+                          "set DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 before the HIP runtime starts")
+        return self._validate_capture(capacity, validate, dev)
+
+    def _recapture(self):
+        """A captured step whose configuration changed (regime, SH degree, parameter tensors, deterministic mode) is captured again."""
+        if self._graph:
+            self._graph = None
+            self.enable_graph(self._capacity)
+
+    def _new_view_counter(self, dev, iteration):
+        """The two device words the first node of a captured step reads: the view counter and the override (-1: none)."""
+        self._vctr = torch.full((1,), int(iteration), dtype=torch.int32, device=dev)
+        self._vovr = torch.full((1,), -1, dtype=torch.int32, device=dev)
+
+    def _prepare_views(self, dev):
+        """What a replay reads its view from: the resident ray tables and targets, the table of view rows, the static camera."""
+        # (rays_d [H*W,3], rays_o [3]) per view and the targets stay resident: the table rows point at them
+        self._rays = [tuple(t.contiguous() for t in camera_rays(cam, dev)) for cam in self.cameras]
+        self._targets_c = [t.contiguous() for t in self.targets]
+        rows = [StaticCamera.pack(cam, self._rays[v][0], self._rays[v][1], self._targets_c[v % len(self._targets_c)])
+                for v, cam in enumerate(self.cameras)]
+        self._vtab = torch.stack(rows).to(dev)
+        self._scam = StaticCamera(self.cameras[0], dev, self._rays[0][0], self._targets_c[0])
+        self._scam.load(self._vtab[0])
+        # the view of a replay is chosen ON THE DEVICE by the first node of the graph (dgs_select_row): step counter + override word.
+        # The host mirrors the counter; a step that asks for another view than the default order's writes the override first.
+        self._dev_select = os.environ.get("DGS_DEVICE_VIEW_SELECT", "1") != "0"
+        self._select_rider = os.environ.get("DGS_SELECT_RIDER", "1") != "0"   # 0: the selection as a node of its own (A/B)
+        self._new_view_counter(dev, self.iteration)
+        self._vctr_host = int(self.iteration)
+        self._sel_stride, self._sel_offset = self.world, self.rank   # row = (counter * stride + offset) mod V
+        self._sgt = self._scam.target
+
+    def _warm_up(self):
+        """Three eager steps of the shape that is about to be captured; returns the side stream they ran on (the capture's stream)."""
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):  # warm-up on a side stream (allocations, lazily created buffers) as torch.cuda.graph requires
+            # ... on a snapshot: the warm-up steps must not train (enable_graph is also called mid-run, by Trainer.grow)
+            snap = self._snapshot()
+            for _ in range(3):
+                if self.views_per_rank > 1:
+                    for j in range(self.views_per_rank):
+                        self._view_of_step(j, self._scam, self._sgt)
+                    self._finish()
+                elif self._split_ok():
+                    self._split_step(self._scam, self._sgt)
+                else:
+                    self._fwd_bwd(self._scam, self._sgt)
+                    self._finish()
+            self._restore(snap)
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        return s
+
+    def _capture_k_views(self, mode):
+        """k views per step: one captured graph per KIND of view -- the first (gradients stored or the bucket cleared, neighbour
+        search), the middle ones (gradients added), the last (added; statistics and loss of the k views closed; single GPU: the
+        update) -- replayed in that order by _replay_views; the exchange and, under data parallelism, the update follow"""
+        k = self.views_per_rank
+        self._gk = [None, None, None]
+        for which, j in ((0, 0), (1, 1), (2, k - 1)):
+            if which == 1 and k < 3:
+                continue
+            g = torch.cuda.CUDAGraph()
+            kw = dict(mode) if which == 0 else dict(mode, pool=self._gk[0].pool())
+            with torch.cuda.graph(g, **kw):
+                self._select_view_node()
+                self._view_of_step(j, self._scam, self._sgt)
+                self._select_consumed()
+                if which == 2 and self.world == 1:
+                    self._finish()
+            self._gk[which] = g
+        self._g1 = self._gk[0]
+        self._sloss = self._kloss
+
+    def _capture_split(self, mode):
+        """data parallel: graph 1a = forward + backward down to the rasterizer inputs (SH gradients final), eager async
+        all-reduce of the SH segment, graph 1b = rest of the backward, eager all-reduce of the rest, graph 2 = update"""
+        if self._shard_ok():
+            # sharded SH update: the deformation head is a graph of its own (graph 0) -- it reads no SH coefficient, so the wait for
+            # the all-gather of the previous step's SH rows sits BEHIND it and that transfer rides under the head's ~75 us
+            self._g0 = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self._g0, **mode):
+                self._select_view_node()
+                self._head = self._forward_head(self._scam)
+                self._select_consumed()
+            with torch.cuda.graph(self._g1, pool=self._g0.pool(), **mode):
+                self._sloss = self._fwd_bwd_a(self._scam, self._sgt, self._head)
+        else:
+            with torch.cuda.graph(self._g1, **mode):
+                self._select_view_node()
+                self._sloss = self._fwd_bwd_a(self._scam, self._sgt)
+                self._select_consumed()
+        self._g1b = torch.cuda.CUDAGraph()
+        if self.split3:
+            with torch.cuda.graph(self._g1b, pool=self._g1.pool(), **mode):
+                self._fwd_bwd_b1()
+            self._g1c = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self._g1c, pool=self._g1.pool(), **mode):
+                self._fwd_bwd_b2()
+        else:
+            with torch.cuda.graph(self._g1b, pool=self._g1.pool(), **mode):
+                self._fwd_bwd_b()
+
+    def _capture_single(self, mode):
+        """one view per step, one graph (single GPU: with the update)"""
+        with torch.cuda.graph(self._g1, **mode):
+            self._select_view_node()
+            self._sloss = self._fwd_bwd(self._scam, self._sgt)   # lives in the graph's pool: rewritten by every replay
+            self._select_consumed()
+            if self.world == 1:
+                self._finish()
+
+    def _capture_updates(self, mode):
+        """data parallel: the updates behind the (eager) collectives as graphs of their own, in graph 1's pool"""
+        self._g2 = self._g2a = self._g2b = None
+        if self.world > 1:
+            if self._split:
+                self._g2a = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self._g2a, pool=self._g1.pool(), **mode):
+                    self._finish_sh()
+                if self.split3:
+                    self._g2b = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(self._g2b, pool=self._g1.pool(), **mode):
+                        self._finish_mid()
+            self._g2 = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self._g2, pool=self._g1.pool(), **mode):
+                self._finish(reduce=False, sh_done=self._split, mid_done=self._split and self.split3)
+
+    # ---- replaying the capture ---------------------------------------------------------------------------------------------
+    def _aim_view(self, tr, counter, v, default):
+        """In front of a replay of trainer (or lane) `tr`: make its first node pick view v.  The device's view counter should read
+        `counter` now -- it does unless the host's count (self._vctr_host, which the CALLER advances: per view in the k-views-added
+        path, once per step over all lanes) was moved: a rewind after skipped steps, a tool -- and `default` is the view the default
+        order gives; a view order of the caller's own writes the override word.  Default order: nothing to do on the host, nothing
+        is launched.  Without the device-side selection: one 256-byte copy (camera matrices, time, the pointers of target / ray table)."""
+        if not self._dev_select:
+            tr._scam.load(self._vtab[v])
+            return
+        if counter != self._vctr_host:
+            tr._vctr.fill_(counter)
+        if v != default:
+            tr._vovr.fill_(v)
+
+    def _replay_view(self, v):
+        """One captured step of one view: the graph(s) enable_graph captured, the data-parallel exchange between them."""
+        it = self.iteration - 1            # the iteration this step belongs to (step() has counted it already)
+        self._aim_view(self, it, v, self._scheduled_view(it))
+        self._vctr_host = it + 1
+        if self._g1b is not None:          # split step: the choreography of the eager one over the graphs' replays
+            third = self._g1c is not None
+            self._split_exchange(self._g0.replay if self._g0 is not None else None, lambda head: self._g1.replay(), self._g1b.replay,
+                                 self._g1c.replay if third else None, self._g2a.replay, self._g2b.replay if third else None, self._g2.replay)
+            return self._sloss
+        self._g1.replay()
+        if self._g2 is not None:
+            self._reduce()
+            self._g2.replay()
+        return self._sloss
+
+    def _replay_views(self, views):
+        """One captured multi-view step (views_per_rank > 1): the lanes' graphs, or the per-view graphs one after the other."""
+        if self._glanes is not None and self._gk is None:
+            return self._step_lanes(views)
+        k = self.views_per_rank
+        it = self.iteration - 1
+        for j, v in enumerate(views):   # this counter counts VIEWS: it * k + j in front of the step's j-th view, every replay counts one
+            self._aim_view(self, it * k + j, v, self._scheduled_view(it, j))
+            self._vctr_host = it * k + j + 1
+            self._gk[0 if j == 0 else (2 if j == k - 1 else 1)].replay()   # first (stores) / middle (adds) / last (adds, closes the statistics)
+        if self._g2 is not None:
+            self._reduce()
+            self._g2.replay()
+        return self._kloss
+
+    def _validate_capture(self, capacity, validate, dev):
+        from diff_surfel_rasterization import _C
+        # validate: render EVERY view once (forward only, nothing trains; ~0.3 ms each) -- a view whose tile lists break the
+        # capacity or the promised list length is found now, not by the step guard in the middle of a run (which would skip
+        # that step, double / withdraw and re-capture).  validate=False leaves it to the guard.
+        if validate:
+            with torch.no_grad():
+                for v in range(len(self.cameras)):
+                    self._scam.load(self._vtab[v])
+                    self._forward(self._scam, self._sgt)
+            self._scam.load(self._vtab[0])
+            torch.cuda.synchronize()
+        reason = self._agree_reason(_C.read_overflow(device=dev))   # (data parallel: one verdict -- a rank re-capturing alone would pair its warm-up collectives with the others' training steps)
+        if reason:
+            if reason & 1 and validate:    # (a broken promise next to it would not change that)
+                raise RuntimeError("rasterizer capacity %d too small for this scene" % capacity)
+            if self._list_hint and (reason & 6 or not reason & 1):   # only the promised list length was exceeded: the tier that fits, capture again
+                self._list_hint = 0 if reason & 4 else self._next_list_hint()
+                self._graph = None
+                return self.enable_graph(capacity, validate=validate)
+
+    def _select_view_node(self):
+        """First node of a captured step (see enable_graph): the view row of this replay, chosen on the device."""
+        if self._dev_select:
+            from . import _ops
+            args = (self._vtab, self._vctr, self._vovr, self._sel_stride, self._sel_offset, self._scam.row)
+            s, d = self.surfels, self.deform
+            if (self._select_rider and self.rasterizer_cls is None and s.get_xyz.is_cuda and self.fuse_deform and hasattr(d, "_node_attrs")
+                    and d.can_assemble(s)):
+                # the deformation's node MLP is the first consumer of the view (its time): the selection rides in that path's first
+                # launch instead of being a node of its own (4 us + the fork behind it: 9 us of the step)
+                d.view_select = args
+            else:
+                _ops.select_row(*args)
+
+    def _select_consumed(self):
+        """A handed-over view selection (_select_view_node) must have been launched by the step that was just built."""
+        if getattr(self.deform, "view_select", None) is not None:
+            self.deform.view_select = None
+            raise RuntimeError("the captured step did not launch its view selection")
+
+    def refresh_knn_mode(self):
+        """Re-evaluate which seeded neighbour search fits the scene (ControlNodes.pick_knn_refine: one host read) and, if the
+        answer changed under a captured step, capture again.  fit() calls it at densification steps."""
+        d = self.deform
+        if not hasattr(d, "pick_knn_refine") or not self.surfels.get_xyz.is_cuda:
+            return False
+        if d.pick_knn_refine(self.surfels):
+            if self._graph:
+                self.enable_graph(self._capacity)
+            return True
+        return False
+
+    def _snapshot(self):
+        sf = self.surfels
+        self._wait_gather()
+        state = [p.detach().clone() for p in self.bucket.params]
+        opt = (self.opt_surfels.exp_avg.clone(), self.opt_surfels.exp_avg_sq.clone(), self.opt_surfels.t.clone(),
+               self.opt_surfels.status.clone())
+        # (sharded SH update: a rank's copy of the SH moments may be current on its own rows only -- the snapshot keeps them as they
+        # are, with the flag that says so)
+        stats = (sf.xyz_gradient_accum.clone(), sf.denom.clone(), sf.max_radii2D.clone(), self._sh_moments_local)
+        if hasattr(self.opt_surfels, "_origin"):   # the per-parameter Adam step origins are optimiser state too (host side)
+            opt = opt + (list(self.opt_surfels._origin),)
+        return state, opt, stats
+
+    @torch.no_grad()
+    def _restore(self, snap):
+        sf = self.surfels
+        state, opt, stats = snap
+        self._wait_gather()
+        if len(stats) > 3:
+            self._sh_moments_local = stats[3]
+        for p, q in zip(self.bucket.params, state):
+            p.copy_(q)
+        self.opt_surfels.exp_avg.copy_(opt[0])
+        self.opt_surfels.exp_avg_sq.copy_(opt[1])
+        self.opt_surfels.t.copy_(opt[2])
+        self.opt_surfels.status.copy_(opt[3])
+        if len(opt) > 4 and hasattr(self.opt_surfels, "_origin") and len(opt[4]) == len(self.opt_surfels._origin):
+            if list(self.opt_surfels._origin) != opt[4]:
+                for i, v in enumerate(opt[4]):
+                    self.opt_surfels._origin[i] = v
+                self.opt_surfels.__dict__.pop("_origin_slices", None)
+        sf.xyz_gradient_accum.copy_(stats[0])
+        sf.denom.copy_(stats[1])
+        sf.max_radii2D.copy_(stats[2])
+        self._resync_guard()
+
+    def set_deterministic(self, on=True):
+        """Bit-reproducible training on the HIP path: every float-atomic sum of the step is replaced by an order-free one -- the
+        backward blend and the skinning backward's node table add 64-bit fixed-point numbers (units of 2^-44) with INTEGER atomics
+        (rasterizer option 7 = 2; dgs_deform_backward accumulate bit 4) instead of float atomics.  Two runs from the same seed then agree
+        bit for bit through densification and opacity resets (tests/test_learning_gpu.py).  Costs ~5-10 % of a step and quantises
+        the blend's partial sums to 6e-14 (a different, equally valid optimisation: kernels_blend.h).  The option lives in the
+        rasterizer context of this trainer's DEVICE; a captured step is re-captured."""
+        from diff_surfel_rasterization import _C
+        on = bool(on)
+        if on == self._deterministic:
+            return
+        dev = self.surfels.get_xyz.device
+        assert dev.type == "cuda" and self.rasterizer_cls is None, "deterministic mode is a mode of the HIP path"
+        self._flush_guard()
+        self._deterministic = on
+        # the long-tile path (four workgroups share a tile's list: sums taken stretch-wise, i.e. other roundings than the serial walk) is
+        # given to the first 256 slots of the longest-first dispatch order, and the order of tiles of EQUAL length class in that
+        # order comes from LDS atomics -- which tiles get it is not reproducible once more than 256 qualify.  Serial walks only.
+        # (the options live in the device's context, which other code may have configured -- DGS_LONG_TILES=0, a caller's own
+        # deterministic = 1: switching the mode off puts back what switching it on found, not the library's defaults.)
+        if on:
+            self._det_saved = (_C.get_option(7, device=dev), _C.get_option(9, device=dev))
+            _C.set_option(7, 2, device=dev)
+            _C.set_option(9, 0, device=dev)
+        else:
+            was7, was9 = self._det_saved
+            _C.set_option(7, was7, device=dev)
+            _C.set_option(9, was9, device=dev)
+        self.deform.fixed_point_tables = on   # the coherent skinning backward's node table: 64-bit fixed-point sums, integer atomics
+        self._recapture()   # (the fixed-point rows of the backward are allocated by the eager warm-up steps enable_graph runs before it captures)
+
+    def set_regime(self, warmup=None, lambda_normal=None, lambda_dist=None):
+        """Move to another stage of the reference's schedule (see __init__).  The regime is part of the captured step (kernel
+        arguments, which launches exist): a change re-captures, two or three times per run.  Returns whether anything changed."""
+        new = (self.warmup if warmup is None else bool(warmup), self.lambda_normal if lambda_normal is None else float(lambda_normal),
+               self.lambda_dist if lambda_dist is None else float(lambda_dist))
+        if new == (self.warmup, self.lambda_normal, self.lambda_dist):
+            return False
+        self._flush_guard()
+        if self.warmup and not new[0] and self.opt_deform is None:
+            # `feature` and the deformation parameters join the optimisation now: torch.optim.Adam (the reference, train_gui.py:281-285,
+            # 427-432) has skipped them so far, so their own step count starts at 1 -- not at the run's count, which would switch
+            # the bias corrections off for moments that start from zero (3-6 x the learning rate for the first few hundred steps)
+            t_now = float(self.opt_surfels.t.item())
+            self.opt_surfels.set_origin(self.n_surfel_params - 1, None, t_now)
+            for i, steps in self._adopted_steps.items():   # ... or continues where an adopted optimiser stood (adopt_deform_state)
+                self.opt_surfels.set_origin(i, i + 1, t_now - steps)
+        self.warmup, self.lambda_normal, self.lambda_dist = new
+        self._recapture()
+        return True
+
+    def oneup_sh_degree(self):
+        """GaussianModel.oneupSHdegree (gaussian_model.py:139-141).  The active degree is an argument of the rasterizer
+        launches, i.e. part of the captured step: re-capture (three times per run at the reference's schedule)."""
+        s = self.surfels
+        if s.active_sh_degree >= s.max_sh_degree:
+            return False
+        self._flush_guard()
+        s.active_sh_degree += 1
+        self._recapture()
+        return True

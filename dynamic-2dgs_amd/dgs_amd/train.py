@@ -9,6 +9,10 @@ own view of the step's batch, and all gradients live in ONE flat fp32 bucket tha
 step over RCCL/xGMI (backend "nccl"; "gloo" in the CPU tests) -- on the HIP path in two asynchronous slices that overlap the
 rest of the backward and the SH update.  The bucket tail carries the densification
 statistics (train_gui.py:411, gaussian_model.py:484-486) so replicas stay identical without a second sum.
+
+This module holds the Trainer -- constructor, state, forward / backward, the update, the step -- and what other files import from it.
+The rest of the class lives in one mixin per concern: guard.py (step guard, overflow recovery), capture.py (HIP-graph capture and
+replay), exchange.py (the data-parallel exchange), lanes.py (concurrent view lanes), surgery.py (densification, reordering, growth).
 """
 import os
 
@@ -17,46 +21,13 @@ import torch.distributed as dist
 
 from . import losses as _losses
 from . import trace
+from .capture import CaptureMixin, StaticCamera  # noqa: F401  (StaticCamera, alias_module: imported from here by other files)
+from .exchange import ExchangeMixin
+from .guard import GuardMixin
+from .lanes import LanesMixin, alias_module  # noqa: F401
 from .losses import training_loss, training_loss_from_allmap
-from .render import camera_rays, render
-
-
-class StaticCamera:
-    """Camera whose tensors are views of ONE fixed 64-float device row: the captured step reads them, `load` refills the
-    row with a single 256-byte copy per view (nine separate copies -- two of them 7.7 MB: the ray table and the target
-    image -- cost 56 us of a 1.4 ms step).  The row also carries two POINTERS (`slots`: target image, ray table) that the
-    loss kernels dereference at run time, so the big per-view arrays stay where they are.
-    row layout (floats): world_view 0:16 | full_proj 16:32 | camera_center 32:35 | fid 35 | rays_o 36:39 | slots 40:44 (2 x int64)"""
-    ROW = 64
-
-    def __init__(self, cam, device, rays_d, target):
-        self.image_height, self.image_width = cam.image_height, cam.image_width
-        self.FoVx, self.FoVy = cam.FoVx, cam.FoVy
-        self.row = torch.zeros(self.ROW, dtype=torch.float32, device=device)
-        self.world_view_transform = self.row[0:16].view(4, 4)
-        self.full_proj_transform = self.row[16:32].view(4, 4)
-        self.camera_center = self.row[32:35]
-        self.fid = self.row[35:36]
-        self.rays_o = self.row[36:39]
-        self.slots = self.row[40:44].view(torch.int64)
-        self.rays_d = rays_d      # placeholders of the right shape: the kernels follow `slots`
-        self.target = target
-
-    @staticmethod
-    def pack(cam, rays_d, rays_o, target):
-        """One table row (CPU float32 tensor) for this view; the tensors it points to must stay alive."""
-        import numpy as np
-        row = np.zeros(StaticCamera.ROW, np.float32)
-        row[0:16] = cam.world_view_transform.detach().cpu().numpy().reshape(-1)
-        row[16:32] = cam.full_proj_transform.detach().cpu().numpy().reshape(-1)
-        row[32:35] = cam.camera_center.detach().cpu().numpy().reshape(-1)
-        row[35] = float(cam.fid.detach().cpu().reshape(-1)[0])
-        row[36:39] = rays_o.detach().cpu().numpy().reshape(-1)
-        row.view(np.int64)[20:22] = [target.data_ptr(), rays_d.data_ptr()]
-        return torch.from_numpy(row)
-
-    def load(self, table_row):
-        self.row.copy_(table_row, non_blocking=True)
+from .render import render
+from .surgery import SurgeryMixin
 
 
 class FlatGradBucket:
@@ -94,28 +65,6 @@ def expon_lr(step, lr_init, lr_final, max_steps):
     return math.exp(math.log(lr_init) * (1 - t) + math.log(lr_final) * t)
 
 
-# per-instance scratch of the two model classes (streams, neighbour seeds, persistent tables, hooks): an alias starts without it
-_ALIAS_SCRATCH = ("_side_stream", "_deferred", "_knn_seed", "_coherent_tables", "_g_attrs", "_pending_reduce", "_join_pending",
-                  "_deferred_active", "view_select", "_graphed", "_graphed_keys", "_screenspace_leaf", "_before_sh_read")
-
-
-def alias_module(m):
-    """A module of the same class and configuration whose parameters are NEW Parameter objects over the SAME storage (values shared,
-    an own .grad each) and whose buffers are the same tensors.  What a second view needs to run its forward and backward next to
-    the first one's: the autograd leaves, the gradient sinks and every per-instance scratch buffer are its own; an in-place update
-    or in-place surgery of the original is visible at once.  (Replacing a Parameter of the original breaks the alias: rebuild it.)"""
-    import copy
-    from collections import OrderedDict
-    c = copy.copy(m)
-    c.__dict__ = dict(m.__dict__)
-    for k in _ALIAS_SCRATCH:
-        c.__dict__.pop(k, None)
-    c._parameters = OrderedDict((n, None if p is None else torch.nn.Parameter(p.data, requires_grad=p.requires_grad)) for n, p in m._parameters.items())
-    c._buffers = OrderedDict(m._buffers)
-    c._modules = OrderedDict((n, None if sub is None else alias_module(sub)) for n, sub in m._modules.items())
-    return c
-
-
 def split_step_allowed(world, overlap_allreduce, hip_fused_path, arap_active):
     """May the data-parallel step be split at the rasterizer inputs (backward half a | SH all-reduce | half b)?
     Half a differentiates the loss with respect to the ASSEMBLED rasterizer inputs only.  The ARAP regulariser reaches the
@@ -124,7 +73,7 @@ def split_step_allowed(world, overlap_allreduce, hip_fused_path, arap_active):
     return bool(world > 1 and overlap_allreduce and hip_fused_path and not arap_active)
 
 
-class Trainer:
+class Trainer(GuardMixin, CaptureMixin, ExchangeMixin, LanesMixin, SurgeryMixin):
     # Learning rates of the reference's exponential schedules at the END of their decay (iteration >= 40000:
     # xyz 1.6e-6 * spatial_lr_scale, deform 1.6e-6; arguments/__init__.py:103-108, scene/deform_model.py:38,
     # utils/general_utils.py get_expon_lr_func), the other groups are constant in the reference.  With the
@@ -141,6 +90,18 @@ class Trainer:
     # captured graph stays valid); on the CPU path the group rates are set before each optimiser step.
     SCHED_POSITION = (0.00016, 0.0000016, 30_000)
     SCHED_DEFORM = (0.00016 * 5, 0.0000016, 40_000)
+    # State that is created on first use (the mixins declare theirs the same way): the defaults say "not there yet".
+    #   opt_surfels, opt_deform: _build_state -- FlatAdam + None (HIP path), or two torch.optim.Adam
+    #   _store_key: what _store_ok's cached verdict (_store_val) was computed for; _unit: dL/dloss = 1 of the fused path's backward
+    #   _late_stats: (pkg, fused) of statistics that _finish launches behind the surfel update
+    #   _half: split step, between half a and half b -- (assembled inputs, their gradients, render package)
+    #   _kx, _kr: k views added -- sum / max of the views' statistics (_stats_accumulate); _arap_gen: generator of the ARAP term's random times
+    opt_surfels = opt_deform = _store_key = _unit = _late_stats = _half = _kx = _kr = _arap_gen = None
+    #   _bucket_clean: the last update cleared the gradients behind its reads (FlatAdam.zero_grads)
+    #   _store_now: the step being built stores its gradients, no fill of the bucket (_forward_head)
+    #   _guard_early: the guard kernel of the step rode in its loss node (_forward)
+    _bucket_clean = _store_now = _guard_early = False
+    _accum_view = 0                   # j > 0 while view j of a k-views-added step is built: producers add
 
     def __init__(self, surfels, deform, cameras, targets, bg_color, deform_lr=LATE_DEFORM_LR, position_lr=LATE_POSITION_LR,
                  fused_adam=None, rasterizer_cls=None, lr_schedule=False, arap=False, views_per_rank=1, shard_optimizer=True,
@@ -194,6 +155,7 @@ class Trainer:
         if lr_schedule:
             position_lr, deform_lr = self.SCHED_POSITION[0], self.SCHED_DEFORM[0]
         self._steps_done = 0
+        self._adopted_steps = {}   # bucket index -> steps an adopted optimiser had taken (adopt_deform_state; used by set_regime)
         self.rasterizer_cls = rasterizer_cls  # None = the HIP operator; tests / the CPU baseline inject the oracle op
         self.cameras, self.targets, self.bg = cameras, targets, bg_color
         self._lrs = (position_lr, deform_lr)
@@ -277,7 +239,7 @@ class Trainer:
                         schedules[i] = (self.SCHED_POSITION[1] * scale, self.SCHED_POSITION[2])
                     elif id(p) in net:
                         schedules[i] = (self.SCHED_DEFORM[1], self.SCHED_DEFORM[2])
-            old = getattr(self, "opt_surfels", None)
+            old = self.opt_surfels
             self.opt_surfels = _ops.FlatAdam(plist, [lr_of[id(p)] for p in plist], self.bucket.flat, patterns=patterns,
                                              schedules=schedules, sched_t0=float(self._steps_done))
             self.opt_deform = None
@@ -299,678 +261,8 @@ class Trainer:
             assert not getattr(surfels, "packed_sh", False), "packed SH needs the flat Adam kernel (two rates inside one parameter)"
             self.opt_surfels = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
             self._spatial = groups[0]['lr'] / position_lr
-            if getattr(self, "opt_deform", None) is None:   # kept across Trainer.grow: the deformation parameters do not move
+            if self.opt_deform is None:   # kept across Trainer.grow: the deformation parameters do not move
                 self.opt_deform = torch.optim.Adam(deform_groups, lr=0.0, eps=1e-15)
-
-    # ---- step guard: a capacity overflow must not train anything -----------------------------------------------------
-    GUARD_LAG = 2     # the host looks at the report of the step issued two steps earlier (already finished: no stall)
-    GUARD_RING = 256  # entries of the pinned report ring (step, skipped flag, skipped so far, loss): also the loss history
-
-    def _init_guard(self, old_opt=None):
-        """Capacity mode has no host read inside the step, so a view whose tile lists do not fit renders as background and
-        only raises a device flag (self._oflag, handed to the rasterizer).  The Adam and statistics kernels read that flag ON
-        THE DEVICE and change nothing when it is set.  Data parallel: the flag rides as element P of the radii tensor through
-        the step's MAX all-reduce (any rank's overflow stops every rank; no extra collective) and the kernels read the reduced
-        copy.  The guard kernel also reports (step, flag, skipped) into a pinned ring that step() polls GUARD_LAG steps
-        later -- the same lag on every rank, so all ranks recover at the same step: double the capacity, re-capture, and
-        redo the skipped views."""
-        dev = self.bucket.flat.device
-        if getattr(self, "_oflag", None) is None:
-            self._oflag = torch.zeros(1, dtype=torch.int32, device=dev)
-            self._ring = torch.zeros(self.GUARD_RING, 4, dtype=torch.float32).pin_memory()
-        # radii of the rendered view (max over the ranks after the all-reduce) + 4 control ints; [P] = overflow flag
-        self._radii = torch.zeros(self.P + 4, dtype=torch.int32, device=dev)
-        self._radii_scratch = None
-        opt = self.opt_surfels
-        opt.skip = self._radii[self.P:self.P + 1] if self.world_size_hint() > 1 else self._oflag
-        opt.host_ring = self._ring
-        if old_opt is not None and hasattr(old_opt, "status"):   # rebuilt state (grow / node densification): counters carry over
-            opt.status.copy_(old_opt.status)
-
-    def world_size_hint(self):
-        return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-
-    def loss_history(self, k):
-        """Losses of the last k steps (oldest first) from the guard kernel's pinned ring -- no copy kernel per step, no
-        synchronisation inside the loop; synchronises here.  Steps that were skipped (capacity overflow) report their loss too."""
-        assert 0 < k <= min(self.GUARD_RING, self._guard_steps), "only the last GUARD_RING steps are kept"
-        torch.cuda.synchronize()
-        out = []
-        for n in range(self._guard_steps - k + 1, self._guard_steps + 1):
-            e = self._ring[n % self.GUARD_RING]
-            assert int(e[0]) == n, "ring entry overwritten"
-            out.append(float(e[3]))
-        return out
-
-    def _check_guard(self):
-        """Poll the report of the guarded step issued GUARD_LAG steps ago; recover if it (or, the flag being sticky, any
-        step since) was skipped."""
-        k = self._guard_steps - self.GUARD_LAG
-        ev = self._guard_events.pop(k, None)
-        if k < 1 or ev is None:
-            return
-        ev.synchronize()
-        e = self._ring[k % self.GUARD_RING]
-        if int(e[0]) != k:
-            # the device's step counter and the host's disagree (something advanced FlatAdam outside step()): resynchronise
-            # and look at the flag itself -- silently ignoring the report would hide an overflow for good
-            self._resync_guard()
-            # (data parallel: only what EVERY rank sees may decide -- the guard kernel's copy of the MAX-reduced flag, not this rank's own)
-            if float(self.opt_surfels.status[0].item()) > 0 or (self.world == 1 and bool(self._oflag.item())):
-                self._recover_overflow()
-            return
-        if float(e[1]) > 0:
-            self._recover_overflow()
-
-    def _flush_guard(self):
-        """Look at every report the step guard has not shown the host yet (step() polls GUARD_LAG steps late) and recover if one of
-        them -- or the sticky flag itself -- says a step was skipped.  Called wherever the trainer is about to re-capture, change
-        the slot layout or save: an overflow of the last two steps must not be captured into a fresh graph as a stale flag, withdraw
-        the list-length promise for good, or be lost with the steps it skipped."""
-        self._wait_gather()
-        if self.opt_deform is not None or getattr(self, "_oflag", None) is None or getattr(self, "_in_recovery", False):
-            return False
-        torch.cuda.synchronize()
-        self._guard_events.clear()
-        skipped = int(self.opt_surfels.status[1].item())
-        # data parallel: the skipped-step count comes from the MAX-reduced flag and is the same on every rank; this rank's own flag is
-        # not (a recovery is collective: every rank must take this branch, or none)
-        if skipped != self._skipped_seen or (self.world == 1 and bool(self._oflag.item())):
-            if self._graph and getattr(self, "_capacity", 0) > 0:
-                self._recover_overflow()
-                return True
-            raise RuntimeError("rasterizer capacity overflow outside capacity mode")
-        return False
-
-    def _recover_overflow(self):
-        from diff_surfel_rasterization import _C
-        torch.cuda.synchronize()
-        skipped = int(self.opt_surfels.status[1].item())
-        redo = skipped - self._skipped_seen
-        self._skipped_seen = skipped
-        if not self._graph or getattr(self, "_capacity", 0) <= 0:
-            raise RuntimeError("rasterizer capacity overflow outside capacity mode")
-        self.iteration -= redo          # the skipped steps changed nothing: their views are rendered again
-        # kernels_preprocess.h overflow_reason: 1 capacity, 2 promised list length, 4 beyond the segmented sort -- the bits of EVERY rank's
-        # flag (the step's MAX all-reduce only says that some rank overflowed, and max(1, 2) drops a bit): all ranks must move to the
-        # same capacity and the same promise, or their captures -- and the collectives inside the capture's warm-up steps -- diverge
-        reason = self._agree_reason(int(self._oflag.item()))
-        self._oflag.zero_()
-        self._guard_events.clear()
-        self.overflow_recoveries += 1
-        self._after_overflow(reason)
-        self._graph = None
-        self._in_recovery = True
-        try:
-            self.enable_graph(self._capacity, validate=False)
-        finally:
-            self._in_recovery = False
-
-    def _ctx_option(self, key, value):
-        """dgs_set_option on the library context this trainer's renders run in: its lane's, or the device's default one."""
-        from diff_surfel_rasterization import _C
-        if self._lane is not None:
-            self._lane.context.set_option(key, value)
-        else:
-            _C.set_option(key, value, device=self.surfels.get_xyz.device)
-
-    def _ctx_overflow_flag(self, flag):
-        from diff_surfel_rasterization import _C
-        if self._lane is not None:
-            self._lane.context.set_overflow_flag(flag)
-        else:
-            _C.set_overflow_flag(flag)
-
-    # ---- k views of a step in flight at the same time (concurrent_views) ---------------------------------------------------------
-    def _concurrent(self):
-        """Are the k views of a step run concurrently, a lane each?  The fully fused HIP path with the flat Adam kernel only."""
-        s = self.surfels
-        return bool(self.concurrent_views and self.views_per_rank > 1 and self._lane_of is None and self.rasterizer_cls is None
-                    and self.opt_deform is None and s.get_xyz.is_cuda and self.fuse_deform and self.deform.can_assemble(s)
-                    and not self._arap_active())
-
-    def _lanes_key(self):
-        """What the lanes were built for: the parameter storage they alias and the configuration they copied."""
-        d, s = self.deform, self.surfels
-        return (tuple(p.data_ptr() for p in self.bucket.params), self.views_per_rank, self.warmup, self.lambda_normal, self.lambda_dist,
-                int(s.active_sh_degree), bool(getattr(d, "coherent_surfels", False)), getattr(d, "knn_refine_mode", None),
-                bool(getattr(d, "fixed_point_tables", False)), bool(self.sh_grad_sink), bool(self.store_grads), self.P)
-
-    def _make_lanes(self):
-        """Lanes 1 .. k - 1: a Trainer each over ALIAS modules (alias_module: same parameter storage, own Parameter objects) with its
-        own gradient bucket, rasterizer context and streams; used for _fwd_bwd only -- the optimiser, the statistics' accumulators,
-        the step guard and the overflow flag are lane 0's (this trainer's).  Rebuilt whenever a parameter was replaced (growth, node
-        densification) or the regime changed."""
-        key = self._lanes_key()
-        if self._lanes is not None and getattr(self, "_lanes_built_for", None) == key:
-            return self._lanes
-        import diff_surfel_rasterization as dsr
-        dev = self.surfels.get_xyz.device
-        lanes = []
-        for j in range(1, self.views_per_rank):
-            sf, df = alias_module(self.surfels), alias_module(self.deform)
-            ln = Trainer(sf, df, self.cameras, self.targets, self.bg, fused_adam=True, views_per_rank=self.views_per_rank, shard_optimizer=False)
-            ln._lane_of, ln._lane = self, dsr.Lane(dev)
-            ln._lane_index = j
-            ln.rank, ln.world = self.rank, self.world
-            ln.warmup, ln.lambda_normal, ln.lambda_dist = self.warmup, self.lambda_normal, self.lambda_dist
-            ln.sh_grad_sink, ln.store_grads, ln.fuse_deform = self.sh_grad_sink, self.store_grads, self.fuse_deform
-            ln._oflag = self._oflag          # ONE overflow flag for all lanes: any lane's overflow skips the step
-            ln._stream = torch.cuda.Stream(dev, priority=int(os.environ.get("DGS_LANE_PRIORITY", "0")))
-            for k_, v_ in (("_deterministic", getattr(self, "_deterministic", False)),):
-                setattr(ln, k_, v_)
-            if getattr(self, "_deterministic", False):
-                ln._lane.context.set_option(7, 2)
-                ln._lane.context.set_option(9, 0)
-            lanes.append(ln)
-        if getattr(self, "_stream0", None) is None:
-            self._stream0 = torch.cuda.Stream(dev, priority=int(os.environ.get("DGS_LANE0_PRIORITY", "0")))
-        self._lanes, self._lanes_built_for = lanes, key
-        return lanes
-
-    def _lane_list(self):
-        """[(lane trainer, its stream)] of all k lanes, lane 0 = this trainer."""
-        others = self._make_lanes()   # (also creates lane 0's stream)
-        return [(self, self._stream0)] + [(ln, ln._stream) for ln in others]
-
-    def _capture_lanes(self, dev):
-        """One captured graph per lane -- view selection, deformation, render, loss, backward, the view's statistics -- on the lane's own
-        stream and in a memory pool of its own (graphs that replay side by side must not share intermediates), and one graph for the
-        update.  Replayed by _step_lanes."""
-        k = self.views_per_rank
-        lanes = self._lane_list()
-        # no fork INSIDE a lane (one-view steps run the node MLP next to the neighbour search and its backward on a side stream): the other
-        # lane is what fills the device here, and ROCm 7.2's graph instantiation segfaults on the nested forks of the one-graph form
-        # (DGS_LANES_FLAT=0 with separate graphs works and measures the same: 0.650 / 0.657 ms per view)
-        if os.environ.get("DGS_LANES_FLAT", "1") != "0":
-            self._overlap_was = bool(self.deform.overlap_streams)   # lane 0 is this trainer's own module: enable_graph puts the switch back
-            for ln, _ in lanes:
-                ln.deform.overlap_streams = False
-        for j, (ln, st) in enumerate(lanes):
-            if ln is not self:   # the lane's own capture state: its row of the view table, its counters -- the big tables are shared
-                ln._capacity, ln._list_hint = self._capacity, self._list_hint
-                ln._ctx_option(2, self._capacity)
-                ln._ctx_option(6, self._list_hint)
-                ln._ctx_overflow_flag(self._oflag)
-                ln._rays, ln._targets_c, ln._vtab = self._rays, self._targets_c, self._vtab
-                ln._scam = StaticCamera(self.cameras[0], dev, self._rays[0][0], self._targets_c[0])
-                ln._scam.load(self._vtab[0])
-                ln._dev_select, ln._select_rider = self._dev_select, self._select_rider
-                ln._vctr = torch.full((1,), int(self.iteration), dtype=torch.int32, device=dev)
-                ln._vovr = torch.full((1,), -1, dtype=torch.int32, device=dev)
-                ln._sgt = ln._scam.target
-            ln._sel_stride, ln._sel_offset = k * self.world, j * self.world + self.rank   # view_for(i, j) = ((i k + j) world + rank) mod V
-        self._vctr_host = int(self.iteration)
-        cur = torch.cuda.current_stream()
-        snap = self._snapshot()
-        for _ in range(3):      # warm-up: allocations, lazily created per-lane buffers -- on a snapshot, nothing trains
-            self._lanes_eager([(ln._scam, ln._sgt) for ln, _ in lanes])
-            self._finish_lanes(eager=True)
-        self._restore(snap)
-        # (the captured update runs the optimiser over two parameter ranges: their block plans are built by a kernel on first use --
-        # before the capture, not inside it)
-        self.opt_surfels._range(0, self.n_surfel_params)
-        self.opt_surfels._range(self.n_surfel_params, len(self.bucket.params))
-        torch.cuda.synchronize()
-        mode = {"capture_error_mode": "thread_local"}
-        self._gall = None
-        one_graph = os.environ.get("DGS_LANES_ONE_GRAPH", "1" if self.world == 1 else "0") != "0" and os.environ.get("DGS_LANES_FLAT", "1") != "0"
-        if one_graph:
-            # ONE graph: the lanes fork from the capture stream and join in front of the update (single GPU: the update is part of
-            # the graph) -- one replay per step, every lane starts at the same moment
-            s0 = self._stream0
-            s0.wait_stream(cur)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=s0, **mode):
-                for ln, st in lanes[1:]:
-                    st.wait_stream(s0)
-                # single GPU: the LAST lane (it starts last and ends last) stops behind its skinning backward -- every per-surfel gradient
-                # of every lane is final there -- and the surfel update runs NEXT TO that lane's node-MLP backward chain, as in the
-                # one-view step, instead of behind it (the update is 68 us of the step's serial tail otherwise)
-                tail_overlap = self.world == 1 and os.environ.get("DGS_LANES_TAIL_OVERLAP", "1") != "0"
-                last_ln, last_st = lanes[-1]
-                for ln, st in lanes:
-                    with torch.cuda.stream(st):
-                        ln._select_view_node()
-                        if tail_overlap and ln is last_ln:
-                            ln._lane_loss = ln._lane_backward_to_surfels(ln._scam, ln._sgt)
-                        else:
-                            ln._lane_loss = ln._fwd_bwd(ln._scam, ln._sgt)
-                        ln._select_consumed()
-                for ln, st in lanes[1:]:
-                    s0.wait_stream(st)
-                if tail_overlap:
-                    loss_first = os.environ.get("DGS_LANES_TAIL_ORDER", "mlp") == "loss"   # (A/B: 0.6250 loss first, 0.6234 chain first, 0.6308 without the overlap)
-                    if loss_first:
-                        self._lanes_loss()
-                    if last_st is not s0:
-                        last_st.wait_stream(s0)          # (the fork; lane 0 as the last lane cannot happen with k > 1)
-                    with torch.cuda.stream(last_st):
-                        last_ln._lane_backward_rest()    # node-MLP backward, weight gradients, this lane's statistics
-                    if not loss_first:
-                        self._lanes_loss()
-                    self._finish_lanes(eager=False, join=last_st)
-                else:
-                    self._lanes_loss()
-                    if self.world == 1:
-                        self._finish_lanes(eager=False)
-            cur.wait_stream(s0)
-            self._gall = g
-            self._glanes = []
-            self._g2 = None
-            if self.world > 1:
-                self._g2 = torch.cuda.CUDAGraph()
-                s = torch.cuda.Stream()
-                s.wait_stream(cur)
-                with torch.cuda.graph(self._g2, stream=s, **mode):
-                    self._finish_lanes(eager=False)
-                cur.wait_stream(s)
-            self._sloss = self._kloss
-            self._gk = self._g1 = self._g1b = self._g0 = None
-            return
-        self._glanes = []
-        for j, (ln, st) in enumerate(lanes):
-            st.wait_stream(cur)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=st, **mode):
-                ln._select_view_node()
-                ln._lane_loss = ln._fwd_bwd(ln._scam, ln._sgt)
-                ln._select_consumed()
-            self._glanes.append(g)
-            cur.wait_stream(st)
-        torch.cuda.synchronize()
-        self._g2 = torch.cuda.CUDAGraph()
-        s = torch.cuda.Stream()
-        s.wait_stream(cur)
-        with torch.cuda.graph(self._g2, stream=s, **mode):
-            self._lanes_loss()
-            self._finish_lanes(eager=False)
-        cur.wait_stream(s)
-        self._sloss = self._kloss
-        self._gk = self._g1 = self._g1b = self._g0 = None
-
-    def _lane_backward_to_surfels(self, cam, gt):
-        """_fwd_bwd of a lane up to the end of autograd's backward (rasterizer + skinning backward): all per-surfel gradients of the
-        lane's bucket are final, the node-MLP backward is still to come (_lane_backward_rest)."""
-        loss, pkg, asm, fused = self._forward(cam, gt)
-        self._note_loss(loss.detach())
-        self._run_backward(lambda: loss.backward(self._unit if fused else None), fused)
-        self._lane_state = (pkg, fused)
-        return loss.detach()
-
-    def _lane_backward_rest(self):
-        pkg, fused = self._lane_state
-        self._lane_state = None
-        d = self.deform
-        if hasattr(d, "finish_backward") and not self.warmup:
-            d.finish_backward(join=True)
-        elif hasattr(d, "run_pending_reduce"):
-            d.run_pending_reduce()
-        self._statistics(pkg, fused)
-
-    def _lanes_eager(self, cams):
-        """The k lanes' forward + backward launched eagerly, each on its stream (the host issues them one after the other, the device
-        overlaps them), joined on the current stream."""
-        cur = torch.cuda.current_stream()
-        lanes = self._lane_list()
-        for (ln, st), (cam, gt) in zip(lanes, cams):
-            st.wait_stream(cur)
-            with torch.cuda.stream(st):
-                ln._lane_loss = ln._fwd_bwd(cam, gt)
-        for ln, st in lanes:
-            cur.wait_stream(st)
-        self._lanes_loss()
-
-    def _lanes_loss(self):
-        """mean of the lanes' losses -> the step's loss (what the guard kernel reports)"""
-        lanes = self._lane_list()
-        if getattr(self, "_kloss", None) is None:
-            self._kloss = torch.zeros(1, dtype=torch.float32, device=self.bucket.flat.device)
-        torch.mean(torch.stack([ln._lane_loss.reshape(()) for ln, _ in lanes]), dim=0, keepdim=True, out=self._kloss)
-        self._note_loss(self._kloss)
-
-    def _step_lanes(self, views):
-        """Replay the k lane graphs side by side, then the update."""
-        k = self.views_per_rank
-        it = self.iteration - 1
-        cur = torch.cuda.current_stream()
-        lanes = self._lane_list()
-        for j, ((ln, st), v) in enumerate(zip(lanes, views)):
-            if self._dev_select:
-                if it != self._vctr_host:
-                    ln._vctr.fill_(it)
-                if v != ((it * k + j) * self.world + self.rank) % len(self.cameras):
-                    ln._vovr.fill_(v)
-            else:
-                ln._scam.load(self._vtab[v])
-        self._vctr_host = it + 1
-        if getattr(self, "_gall", None) is not None:
-            self._gall.replay()
-            if self.world > 1:
-                self._lanes_fold()
-                self._reduce()
-                self._g2.replay()
-            return self._kloss
-        for (ln, st), g in zip(lanes, self._glanes):
-            st.wait_stream(cur)
-            with torch.cuda.stream(st):
-                g.replay()
-        for ln, st in lanes:
-            cur.wait_stream(st)
-        if self.world > 1:
-            self._lanes_fold()
-            self._reduce()
-        self._g2.replay()
-        return self._kloss
-
-    def _lanes_fold(self):
-        """Data parallel: the exchange works on ONE bucket -- add the other lanes' gradients and statistics into lane 0's first."""
-        for ln in self._make_lanes():
-            self.bucket.flat.add_(ln.bucket.flat)
-            torch.maximum(self._radii, ln._radii, out=self._radii)
-
-    def _agree_reason(self, reason):
-        """Overflow reason bits OR-ed over the ranks (collective: every rank calls it at the same point).  The bits travel as three
-        0/1 words through a MAX all-reduce -- RCCL has no bitwise OR reduction."""
-        if self.world > 1 and not self.no_collectives and dist.is_initialized():
-            bits = torch.tensor([reason & 1, (reason >> 1) & 1, (reason >> 2) & 1], dtype=torch.int32, device=self.bucket.flat.device)
-            dist.all_reduce(bits, op=dist.ReduceOp.MAX)
-            b = bits.tolist()
-            reason = (reason & ~7) | b[0] | (b[1] << 1) | (b[2] << 2)
-        return reason
-
-    # ---- whole-step HIP graph ------------------------------------------------------------------------------------
-    def enable_graph(self, capacity, validate=True):
-        """Capture deform -> render -> loss -> backward (-> Adam when single-GPU) into HIP graphs and replay them per
-        step: the step is ~400 small launches and otherwise bound by the host, not the GPU.  Needs the rasterizer's
-        capacity mode (`capacity` list entries; no device->host read inside the step).  Per view, one 256-byte row (camera,
-        time, pointers of target image and ray table) is copied into a static buffer before each replay.  Under data
-        parallelism the all-reduce stays outside the graphs."""
-        import os
-        from diff_surfel_rasterization import _C
-        assert self.rasterizer_cls is None and self.opt_deform is None, "graph capture is for the HIP operator with the flat Adam kernel"
-        assert not self._mask_terms(), "a ground-truth-mask term is active (random backgrounds, a second render): capture the step once it is not"
-        if self.arap:
-            from .arap import lambda_arap
-            assert lambda_arap(self.iteration + 1) == 0, "the ARAP regulariser is still active: capture the step after iteration 20000"
-        # (Rounds 1-4 refused to capture unless DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 was in the environment: ROCm 7.2's default replay path --
-        # pre-recorded AQL packets -- ran a memset node of the step out of order now and then.  The step has had no memset / fill node
-        # since round 4, and tools/diag/graph_knob_probe.py found 2000 replays of the metric step clean with the knob at either value
-        # (round 5: twin 8.6e-6 / 1.2e-5, the same two guard-recovery steps in both series), so the requirement is gone; bench.py and
-        # the tests still default the knob to 0, the configuration every committed number was measured in.)
-        dev = self.surfels.get_xyz.device
-        self._wait_gather()        # (sharded data-parallel step: the SH rows of the last step's update may still be on the wire)
-        if getattr(self, "_overlap_was", None) is not None:   # a capture of concurrent lanes ran this module without its inner forks (_capture_lanes)
-            self.deform.overlap_streams, self._overlap_was = self._overlap_was, None
-        if self._graph:            # a live capture is being replaced: settle what its last steps reported first
-            if self._flush_guard():
-                return             # the recovery re-captured already (with a larger capacity / without the promise)
-        if hasattr(self.deform, "pick_knn_refine"):
-            self.deform.pick_knn_refine(self.surfels)   # the neighbour-search kernel that fits the scene now is baked into the capture
-        self._capacity = int(capacity)
-        self._ctx_option(2, int(capacity))   # capacity mode (the context of THIS trainer's device -- or lane --, whatever the caller's current device is)
-        # promise of the longest tile list (dgs_set_option key 6): one sort launch instead of three.  A frame that breaks it
-        # counts as an overflow: at capture time (below) and in the step guard the promise is withdrawn first, the capacity
-        # doubled only if that was not the reason
-        if not hasattr(self, "_list_hint"):
-            self._list_hint = 2048
-        self._ctx_option(6, self._list_hint)
-        if getattr(self, "_oflag", None) is not None:
-            self._ctx_overflow_flag(self._oflag)   # the captured launches keep THIS trainer's flag
-            if not getattr(self, "_in_recovery", False):
-                self._oflag.zero_()             # read_overflow below reports overflows of THIS capture only
-        # (rays_d [H*W,3], rays_o [3]) per view and the targets stay resident: the table rows point at them
-        self._rays = [tuple(t.contiguous() for t in camera_rays(cam, dev)) for cam in self.cameras]
-        self._targets_c = [t.contiguous() for t in self.targets]
-        rows = [StaticCamera.pack(cam, self._rays[v][0], self._rays[v][1], self._targets_c[v % len(self._targets_c)])
-                for v, cam in enumerate(self.cameras)]
-        self._vtab = torch.stack(rows).to(dev)
-        self._scam = StaticCamera(self.cameras[0], dev, self._rays[0][0], self._targets_c[0])
-        self._scam.load(self._vtab[0])
-        # the view of a replay is chosen ON THE DEVICE by the first node of the graph (dgs_select_row): step counter + override word.
-        # The host mirrors the counter; a step that asks for another view than the default order's writes the override first.
-        self._dev_select = os.environ.get("DGS_DEVICE_VIEW_SELECT", "1") != "0"
-        self._select_rider = os.environ.get("DGS_SELECT_RIDER", "1") != "0"   # 0: the selection as a node of its own (A/B)
-        self._vctr = torch.full((1,), int(self.iteration), dtype=torch.int32, device=dev)
-        self._vovr = torch.full((1,), -1, dtype=torch.int32, device=dev)
-        self._vctr_host = int(self.iteration)
-        self._sel_stride, self._sel_offset = self.world, self.rank   # row = (counter * stride + offset) mod V
-        self._sgt = self._scam.target
-        if self._concurrent():
-            self._capture_lanes(dev)
-            self._graph = True
-            return self._validate_capture(capacity, validate, dev)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):  # warm-up on a side stream (allocations, lazily created buffers) as torch.cuda.graph requires
-            # ... on a snapshot: the warm-up steps must not train (enable_graph is also called mid-run, by Trainer.grow)
-            snap = self._snapshot()
-            for _ in range(3):
-                if self.views_per_rank > 1:
-                    for j in range(self.views_per_rank):
-                        self._view_of_step(j, self._scam, self._sgt)
-                    self._finish()
-                elif self._split_ok():
-                    self._split_step(self._scam, self._sgt)
-                else:
-                    self._fwd_bwd(self._scam, self._sgt)
-                    self._finish()
-            self._restore(snap)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        self._g1 = torch.cuda.CUDAGraph()
-        self._g1b = None
-        self._g0 = None
-        self._glanes = None
-        # thread-local capture mode: with a process group alive, the collective library's watchdog thread polls events while
-        # this thread captures; under the default ("global") mode such a call from ANOTHER thread invalidates the capture
-        # and the watchdog dies with the error (seen once in three runs on ROCm 7 / RCCL 2.26)
-        # capture ON the warm-up stream: per-stream persistent buffers created by the warm-up steps (the coherent skinning table of
-        # _ops._FusedDeform.backward) are found again instead of being allocated -- and zero-filled on every replay -- inside the graph
-        mode = {"capture_error_mode": "thread_local", "stream": s}
-        self._split = self._split_ok()
-        self._gk = None
-        if self.views_per_rank > 1:
-            # k views per step: one captured graph per KIND of view -- the first (gradients stored or the bucket cleared, neighbour
-            # search), the middle ones (gradients added), the last (added; statistics and loss of the k views closed; single GPU: the
-            # update) -- replayed in that order by _step_views; the exchange and, under data parallelism, the update follow
-            k = self.views_per_rank
-            self._gk = [None, None, None]
-            for which, j in ((0, 0), (1, 1), (2, k - 1)):
-                if which == 1 and k < 3:
-                    continue
-                g = torch.cuda.CUDAGraph()
-                kw = dict(mode) if which == 0 else dict(mode, pool=self._gk[0].pool())
-                with torch.cuda.graph(g, **kw):
-                    self._select_view_node()
-                    self._view_of_step(j, self._scam, self._sgt)
-                    self._select_consumed()
-                    if which == 2 and self.world == 1:
-                        self._finish()
-                self._gk[which] = g
-            self._g1 = self._gk[0]
-            self._sloss = self._kloss
-        elif self._split:
-            # data parallel: graph 1a = forward + backward down to the rasterizer inputs (SH gradients final), eager async
-            # all-reduce of the SH segment, graph 1b = rest of the backward, eager all-reduce of the rest, graph 2 = update
-            if self._shard_ok():
-                # sharded SH update: the deformation head is a graph of its own (graph 0) -- it reads no SH coefficient, so the wait for
-                # the all-gather of the previous step's SH rows sits BEHIND it and that transfer rides under the head's ~75 us
-                self._g0 = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self._g0, **mode):
-                    self._select_view_node()
-                    self._head = self._forward_head(self._scam)
-                    self._select_consumed()
-                with torch.cuda.graph(self._g1, pool=self._g0.pool(), **mode):
-                    self._sloss = self._fwd_bwd_a(self._scam, self._sgt, self._head)
-            else:
-                with torch.cuda.graph(self._g1, **mode):
-                    self._select_view_node()
-                    self._sloss = self._fwd_bwd_a(self._scam, self._sgt)
-                    self._select_consumed()
-            self._g1b = torch.cuda.CUDAGraph()
-            self._g1c = None
-            if self.split3:
-                with torch.cuda.graph(self._g1b, pool=self._g1.pool(), **mode):
-                    self._fwd_bwd_b1()
-                self._g1c = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self._g1c, pool=self._g1.pool(), **mode):
-                    self._fwd_bwd_b2()
-            else:
-                with torch.cuda.graph(self._g1b, pool=self._g1.pool(), **mode):
-                    self._fwd_bwd_b()
-        else:
-            with torch.cuda.graph(self._g1, **mode):
-                self._select_view_node()
-                self._sloss = self._fwd_bwd(self._scam, self._sgt)   # lives in the graph's pool: rewritten by every replay
-                self._select_consumed()
-                if self.world == 1:
-                    self._finish()
-        self._g2 = self._g2a = self._g2b = None
-        if self.world > 1:
-            if self._split:
-                self._g2a = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self._g2a, pool=self._g1.pool(), **mode):
-                    self._finish_sh()
-                if self.split3:
-                    self._g2b = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(self._g2b, pool=self._g1.pool(), **mode):
-                        self._finish_mid()
-            self._g2 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._g2, pool=self._g1.pool(), **mode):
-                self._finish(reduce=False, sh_done=self._split, mid_done=self._split and self.split3)
-        self._graph = True
-        if os.environ.get("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "") != "0" and not getattr(self, "_store_now", False):
-            # (ADVICE r05) rounds 1-4 refused to capture without the knob; the requirement went when the DEFAULT step lost its last
-            # memset node -- this captured step still has one (the bucket's fill: gradients are not stored in place here), and ROCm 7.2's
-            # packet-replay path ran such nodes out of order now and then (an L1 term of exactly 0, or 1e18 gradients)
-            import warnings
-            warnings.warn("captured step contains fill nodes and DEBUG_CLR_GRAPH_PACKET_CAPTURE is not 0: ROCm 7.2 has replayed such nodes out of order; "
-                          "set DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 before the HIP runtime starts")
-        return self._validate_capture(capacity, validate, dev)
-
-    def _validate_capture(self, capacity, validate, dev):
-        from diff_surfel_rasterization import _C
-        # validate: render EVERY view once (forward only, nothing trains; ~0.3 ms each) -- a view whose tile lists break the
-        # capacity or the promised list length is found now, not by the step guard in the middle of a run (which would skip
-        # that step, double / withdraw and re-capture).  validate=False leaves it to the guard.
-        if validate:
-            with torch.no_grad():
-                for v in range(len(self.cameras)):
-                    self._scam.load(self._vtab[v])
-                    self._forward(self._scam, self._sgt)
-            self._scam.load(self._vtab[0])
-            torch.cuda.synchronize()
-        reason = self._agree_reason(_C.read_overflow(device=dev))   # (data parallel: one verdict -- a rank re-capturing alone would pair its warm-up collectives with the others' training steps)
-        if reason:
-            if reason & 1 and validate:    # (a broken promise next to it would not change that)
-                raise RuntimeError("rasterizer capacity %d too small for this scene" % capacity)
-            if self._list_hint and (reason & 6 or not reason & 1):   # only the promised list length was exceeded: the tier that fits, capture again
-                self._list_hint = 0 if reason & 4 else self._next_list_hint()
-                self._graph = None
-                return self.enable_graph(capacity, validate=validate)
-
-    # Promise of the longest tile list (dgs_set_option key 6) in the tiers of the library's sort kernels: up to 2048 entries one
-    # launch, up to 57 344 (28 segments of 2048 + merge) three, no promise (0) four.  A view that breaks the promise
-    # moves the trainer one tier up -- a densified scene with lists of a few thousand entries keeps the cheap tiers it fits.
-    LIST_HINT_TIERS = (2048, 57344, 0)
-
-    def _after_overflow(self, reason):
-        """The next configuration after a frame that did not fit, from the reason bits the kernels left in the flag: a broken promise
-        moves the list-length tier (straight to 'no promise' when the list is beyond the segmented sort), a full buffer doubles the
-        capacity -- both in ONE recovery when both happened.  reason == 0 (flag already consumed): the order of rounds 3-4, promise first."""
-        hint = getattr(self, "_list_hint", 0)
-        if reason & 6 and hint:
-            self._list_hint = 0 if reason & 4 else self._next_list_hint()
-        if reason & 1:
-            self._capacity = 2 * self._capacity
-        if not reason & 7:
-            if hint:
-                self._list_hint = self._next_list_hint()
-            else:
-                self._capacity = 2 * self._capacity
-
-    def _next_list_hint(self):
-        t = self.LIST_HINT_TIERS
-        cur = getattr(self, "_list_hint", 0)
-        return t[t.index(cur) + 1] if cur in t and cur != 0 else 0
-
-    def _select_view_node(self):
-        """First node of a captured step (see enable_graph): the view row of this replay, chosen on the device."""
-        if self._dev_select:
-            from . import _ops
-            args = (self._vtab, self._vctr, self._vovr, self._sel_stride, self._sel_offset, self._scam.row)
-            s, d = self.surfels, self.deform
-            if (self._select_rider and self.rasterizer_cls is None and s.get_xyz.is_cuda and self.fuse_deform and hasattr(d, "_node_attrs")
-                    and d.can_assemble(s)):
-                # the deformation's node MLP is the first consumer of the view (its time): the selection rides in that path's first
-                # launch instead of being a node of its own (4 us + the fork behind it: 9 us of the step)
-                d.view_select = args
-            else:
-                _ops.select_row(*args)
-
-    def _select_consumed(self):
-        """A handed-over view selection (_select_view_node) must have been launched by the step that was just built."""
-        if getattr(self.deform, "view_select", None) is not None:
-            self.deform.view_select = None
-            raise RuntimeError("the captured step did not launch its view selection")
-
-    def refresh_knn_mode(self):
-        """Re-evaluate which seeded neighbour search fits the scene (ControlNodes.pick_knn_refine: one host read) and, if the
-        answer changed under a captured step, capture again.  fit() calls it at densification steps."""
-        d = self.deform
-        if not hasattr(d, "pick_knn_refine") or not self.surfels.get_xyz.is_cuda:
-            return False
-        if d.pick_knn_refine(self.surfels):
-            if self._graph:
-                self.enable_graph(self._capacity)
-            return True
-        return False
-
-    def _snapshot(self):
-        sf = self.surfels
-        self._wait_gather()
-        state = [p.detach().clone() for p in self.bucket.params]
-        opt = (self.opt_surfels.exp_avg.clone(), self.opt_surfels.exp_avg_sq.clone(), self.opt_surfels.t.clone(),
-               self.opt_surfels.status.clone())
-        # (sharded SH update: a rank's copy of the SH moments may be current on its own rows only -- the snapshot keeps them as they
-        # are, with the flag that says so)
-        stats = (sf.xyz_gradient_accum.clone(), sf.denom.clone(), sf.max_radii2D.clone(), self._sh_moments_local)
-        if hasattr(self.opt_surfels, "_origin"):   # the per-parameter Adam step origins are optimiser state too (host side)
-            opt = opt + (list(self.opt_surfels._origin),)
-        return state, opt, stats
-
-    @torch.no_grad()
-    def _restore(self, snap):
-        sf = self.surfels
-        state, opt, stats = snap
-        self._wait_gather()
-        if len(stats) > 3:
-            self._sh_moments_local = stats[3]
-        for p, q in zip(self.bucket.params, state):
-            p.copy_(q)
-        self.opt_surfels.exp_avg.copy_(opt[0])
-        self.opt_surfels.exp_avg_sq.copy_(opt[1])
-        self.opt_surfels.t.copy_(opt[2])
-        self.opt_surfels.status.copy_(opt[3])
-        if len(opt) > 4 and hasattr(self.opt_surfels, "_origin") and len(opt[4]) == len(self.opt_surfels._origin):
-            if list(self.opt_surfels._origin) != opt[4]:
-                for i, v in enumerate(opt[4]):
-                    self.opt_surfels._origin[i] = v
-                self.opt_surfels.__dict__.pop("_origin_slices", None)
-        sf.xyz_gradient_accum.copy_(stats[0])
-        sf.denom.copy_(stats[1])
-        sf.max_radii2D.copy_(stats[2])
-        self._resync_guard()
-
-    def _resync_guard(self):
-        """The guard kernel numbers its reports with the DEVICE step counter (status[2]); whoever moves that counter behind the
-        trainer's back -- a restored snapshot, a tool that drives FlatAdam.step directly -- must bring the host's copy along, or
-        no report would ever match its ring slot again (and a sticky overflow would freeze training unnoticed)."""
-        if getattr(self, "opt_deform", 1) is None and hasattr(self.opt_surfels, "status"):
-            torch.cuda.synchronize()
-            self._guard_steps = int(self.opt_surfels.status[2].item())
-            self._guard_events.clear()
 
     def _forward_head(self, cam):
         """The forward in FRONT of the rasterizer: gradient-bucket handling and the deformation (neighbour search, node MLP, skinning,
@@ -989,11 +281,11 @@ class Trainer:
         t = d.expand_time(cam.fid)
         fused = self.rasterizer_cls is None and s.get_xyz.is_cuda and not self._mask_terms()
         assemble = fused and self.fuse_deform and d.can_assemble(s)
-        adding = getattr(self, "_accum_view", 0) > 0   # view 2 .. k of a multi-view step: every producer ADDS to what the earlier views left
+        adding = self._accum_view > 0   # view 2 .. k of a multi-view step: every producer ADDS to what the earlier views left
         self._store_now = bool(assemble and torch.is_grad_enabled() and self._store_ok()) and not adding
         if hasattr(d, "grad_sink") and d.grad_sink:
             d.grad_sink = "store" if self._store_now else True
-        if not adding and not self._store_now and not (getattr(self, "_bucket_clean", False) and self.opt_deform is None and self.opt_surfels.zero_grads):
+        if not adding and not self._store_now and not (self._bucket_clean and self.opt_deform is None and self.opt_surfels.zero_grads):
             self.bucket.zero()
         if hasattr(d, "reuse_knn"):
             d.reuse_knn = adding             # the surfels and nodes have not moved since the step's first view: its neighbours stand
@@ -1032,7 +324,7 @@ class Trainer:
         # the loss node produces its gradient images in the forward (regularisers: value and gradient in one kernel)
         # single GPU: the step guard rides in the loss node (the thread that writes the loss runs it): everything it reads exists
         # then, and the surfels' Adam update later starts right behind the skinning backward (_finish: advance=False)
-        ride = (fused and torch.is_grad_enabled() and self.world == 1 and self.opt_deform is None and getattr(self, "_oflag", None) is not None
+        ride = (fused and torch.is_grad_enabled() and self.world == 1 and self.opt_deform is None and self._oflag is not None
                 and not self._arap_active() and _losses.FUSE_PHOTOMETRIC and self.views_per_rank == 1)
         with trace.stage("dgs.loss"):
             loss = (training_loss_from_allmap(pkg["render"], pkg["allmap"], cam, gt, unit_grad=True, guard=self.opt_surfels if ride else None, **lam)
@@ -1051,10 +343,10 @@ class Trainer:
             from . import arap
             lam = arap.lambda_arap(self.iteration)       # train_gui.py:315-316, utils/time_utils.py:1228-1232
             if lam > 0 and self.iteration > self.arap_from:
-                if getattr(self, "_arap_gen", None) is None:
+                if self._arap_gen is None:
                     self._arap_gen = torch.Generator(device=s.get_xyz.device).manual_seed(1234 + self.rank)
                 loss = loss + lam * arap.arap_loss(self.deform, generator=self._arap_gen)
-        if fused and getattr(self, "_unit", None) is None:
+        if fused and self._unit is None:
             self._unit = torch.ones((), dtype=loss.dtype, device=loss.device)
         return loss, pkg, asm, fused
 
@@ -1085,7 +377,7 @@ class Trainer:
         # id cannot be reused), and the public switches a caller may flip between steps
         key = (self.bucket, self.opt_surfels, s.feature.shape[1], bool(self.sh_grad_sink), bool(getattr(d, "defer_mlp_backward", False)),
                bool(getattr(d, "grad_sink", False)), bool(getattr(d, "overlap_streams", False)))
-        old = getattr(self, "_store_key", None)
+        old = self._store_key
         if old is None or len(old) != len(key) or any(a is not b and a != b for a, b in zip(old, key)):
             ok = (getattr(s, "packed_sh", False) and self.sh_grad_sink and self.n_sh > 0 and getattr(d, "defer_mlp_backward", False)
                   and bool(getattr(d, "grad_sink", False)) and s.feature.shape[1] == d.hyper_dim)
@@ -1104,18 +396,18 @@ class Trainer:
         s = self.surfels
         # (views 2 .. k of a multi-view step: the sink STORES the rows of the visible surfels, it does not add to them -- those views
         # take the operator's own dL/dSH tensor and autograd adds it to the bucket view: one 4 P M-byte pass more per extra view)
-        if fused and getattr(s, "packed_sh", False) and self.sh_grad_sink and not getattr(self, "_accum_view", 0) and self._lane is not None:
+        if fused and getattr(s, "packed_sh", False) and self.sh_grad_sink and not self._accum_view and self._lane is not None:
             # a lane's sink is a field of its own Lane object: nothing device-wide, nothing keyed by the (shared) parameter storage
-            self._lane.sink, self._lane.all_rows = s._features.grad, bool(getattr(self, "_store_now", False))
+            self._lane.sink, self._lane.all_rows = s._features.grad, bool(self._store_now)
             try:
                 return fn()
             finally:
                 self._lane.sink = None
-        if fused and getattr(s, "packed_sh", False) and self.sh_grad_sink and not getattr(self, "_accum_view", 0):
+        if fused and getattr(s, "packed_sh", False) and self.sh_grad_sink and not self._accum_view:
             import diff_surfel_rasterization as dsr
             # the sink belongs to THIS trainer's SH parameter (keyed by the tensor the forward was given): other trainers on the
             # device keep theirs, and removing it afterwards removes nothing else
-            dsr.set_sh_grad_sink(s._features.grad, all_rows=getattr(self, "_store_now", False), shs=s._features)
+            dsr.set_sh_grad_sink(s._features.grad, all_rows=self._store_now, shs=s._features)
             try:
                 return fn()
             finally:
@@ -1134,7 +426,7 @@ class Trainer:
     def _statistics(self, pkg, fused, early_radii=False):
         with torch.no_grad():
             # densification statistics of this view into the bucket tail (summed over ranks)
-            if getattr(self, "_radii", None) is None:
+            if self._radii is None:
                 self._radii = torch.zeros(self.P + 4, dtype=pkg["radii"].dtype, device=pkg["radii"].device)
             if fused:
                 from . import _ops
@@ -1143,7 +435,7 @@ class Trainer:
                     if self._radii_scratch is None:
                         self._radii_scratch = torch.empty_like(self._radii)
                     radii_vis = self._radii_scratch
-                elif self.world > 1 and getattr(self, "_oflag", None) is not None:
+                elif self.world > 1 and self._oflag is not None:
                     self._radii[self.P:self.P + 1].copy_(self._oflag)
                 _ops.densify_view(pkg["radii"], pkg["viewspace_points"].grad, self.bucket.extra[:self.P], self.bucket.extra[self.P:2 * self.P],
                                   radii_vis)
@@ -1228,180 +520,23 @@ class Trainer:
         self._statistics(pkg, True, early_radii=True)
         self._half = None
 
-    def _n_mid(self):
-        """Elements of the second bucket segment: the surfel parameters behind the SH coefficients."""
-        return sum(p.numel() for p in self.bucket.params[1:self.n_surfel_params])
-
-    class _NoWork:
-        """stand-in for the work handle of a collective that was not issued (Trainer.no_collectives)"""
-        @staticmethod
-        def wait():
-            return True
-
-    class _Bf16Work:
-        """work handle of a slice that crossed the wire as bfloat16: wait() = the collective, then the copy back into the fp32 bucket"""
-        def __init__(self, work, dst, src):
-            self.work, self.dst, self.src = work, dst, src
-
-        def wait(self):
-            self.work.wait()
-            self.dst.copy_(self.src)
-            return True
-
-    def _sum_slice_start(self, lo, hi):
-        """async all-reduce (SUM) of bucket.flat[lo:hi]; with wire_bf16 through a persistent bfloat16 copy of the slice"""
-        sl = self.bucket.flat[lo:hi]
-        if not self.wire_bf16:
-            return dist.all_reduce(sl, op=dist.ReduceOp.SUM, async_op=True)
-        wire = getattr(self, "_wire", None)
-        if wire is None or wire.numel() != self.bucket.flat.numel() or wire.device != sl.device:
-            wire = self._wire = torch.empty(self.bucket.flat.numel(), dtype=torch.bfloat16, device=sl.device)
-        w = wire[lo:hi]
-        w.copy_(sl)
-        return self._Bf16Work(dist.all_reduce(w, op=dist.ReduceOp.SUM, async_op=True), sl, w)
-
-    # ---- sharded SH update (data parallel, split step) ------------------------------------------------------------------
-    def _shard_ok(self):
-        """Does the split step hand the SH update to the rows' owners (Trainer.shard_optimizer)?  Needs equal row ranges."""
-        if not (self.shard_optimizer and dist.is_available() and dist.is_initialized() and self._split_ok()):
-            return False
-        return self.P % dist.get_world_size() == 0 and self.n_sh % self.P == 0
-
-    def _shard_range(self):
-        """ELEMENT range of the SH segment (bucket and parameter alike) this rank owns: rows [rank P / N, (rank + 1) P / N)."""
-        n, r = dist.get_world_size(), dist.get_rank()
-        c = self.n_sh // n
-        return r * c, (r + 1) * c
-
-    def _scatter_sh_start(self):
-        """async reduce-scatter (SUM) of the SH gradients, in place: this rank's rows of the bucket receive the sum over the ranks
-        (the other rows keep this rank's own contribution and are overwritten by the next backward).  With wire_bf16 through the
-        persistent bfloat16 copy, like _sum_slice_start."""
-        lo, hi = self._shard_range()
-        sl = self.bucket.flat[:self.n_sh]
-        if not self.wire_bf16:
-            return dist.reduce_scatter_tensor(sl[lo:hi], sl, op=dist.ReduceOp.SUM, async_op=True)
-        wire = getattr(self, "_wire", None)
-        if wire is None or wire.numel() != self.bucket.flat.numel() or wire.device != sl.device:
-            wire = self._wire = torch.empty(self.bucket.flat.numel(), dtype=torch.bfloat16, device=sl.device)
-        w = wire[:self.n_sh]
-        w.copy_(sl)
-        return self._Bf16Work(dist.reduce_scatter_tensor(w[lo:hi], w, op=dist.ReduceOp.SUM, async_op=True), sl[lo:hi], w[lo:hi])
-
-    def _gather_sh_start(self):
-        """async all-gather of the SH rows every rank has just updated, IN PLACE into the parameter.  Nothing of this step reads the SH
-        coefficients any more; the next reader is the next step's preprocess kernel, behind that step's deformation head
-        (_wait_gather sits between the two) -- or whoever calls settle_shards()."""
-        self._sh_moments_local = True
-        if self.no_collectives:
-            return
-        f = self.surfels._features.data.view(-1)
-        lo, hi = self._shard_range()
-        self._ag_work = dist.all_gather_into_tensor(f, f[lo:hi], async_op=True)
-
-    def _wait_gather(self):
-        """The current stream waits for the outstanding all-gather of the SH coefficients (if any)."""
-        if self._ag_work is not None:
-            self._ag_work.wait()
-            self._ag_work = None
-
-    def settle_shards(self):
-        """Make this rank's copy of everything complete again: wait for the SH all-gather and, if the SH moments are only current
-        on their owners' rows, all-gather them too (two collectives: EVERY rank must call this at the same point -- it is called
-        by whatever reads moments across rows or replaces the optimiser state: densification, reordering, growth, checkpoints)."""
-        self._wait_gather()
-        if self._sh_moments_local and self.opt_deform is None and dist.is_available() and dist.is_initialized() and not self.no_collectives:
-            lo, hi = self._shard_range()
-            a = self.opt_surfels._offsets[0]
-            for m in (self.opt_surfels.exp_avg, self.opt_surfels.exp_avg_sq):
-                seg = m[a:a + self.n_sh]
-                dist.all_gather_into_tensor(seg, seg[lo:hi])
-        self._sh_moments_local = False
-
-    def _reduce_mid_start(self):
-        if self.no_collectives:
-            return self._NoWork
-        return self._sum_slice_start(self.n_sh, self.n_sh + self._n_mid())
-
-    def _reduce_tail_start(self):
-        if self.no_collectives:
-            return []
-        return [dist.all_reduce(self.bucket.flat[self.n_sh + self._n_mid():], op=dist.ReduceOp.SUM, async_op=True)]
-
-    def _finish_mid(self):
-        """Third split: the surfel parameters behind the SH coefficients, as soon as THEIR all-reduce is in."""
-        with torch.no_grad():
-            self.opt_surfels.grad_scale = 1.0 / self.world
-            self.opt_surfels.step(1, self.n_surfel_params - 1 if self.warmup else self.n_surfel_params, advance=False)
-
-    def _reduce_sh_start(self):
-        if self.no_collectives:
-            return self._NoWork
-        if self._shard_ok():
-            return self._scatter_sh_start()
-        return self._sum_slice_start(0, self.n_sh)
-
-    def _reduce_radii_start(self):
-        if self.no_collectives:
-            return self._NoWork
-        return dist.all_reduce(self._radii, op=dist.ReduceOp.MAX, async_op=True)
-
-    def _reduce_rest_start(self):
-        if self.no_collectives:
-            return []
-        return [dist.all_reduce(self.bucket.flat[self.n_sh:], op=dist.ReduceOp.SUM, async_op=True)]
-
-    def wire_bytes_per_step(self):
-        """Bytes each rank hands to the collectives per step (payload of the all-reduces; what actually crosses the links is
-        2 (n-1)/n times that for a ring).  {'sh': SH gradients (all-reduced while the rest of the backward runs), 'rest': all
-        other gradients + the densification statistics of the view, 'radii': int32 radii + the overflow flag (MAX)}."""
-        n_flat = self.bucket.flat.numel()
-        n_radii = self.P + 4
-        sh = self.n_sh if self._split_ok() else 0
-        big = 2 if (self.wire_bf16 and sh) else 4   # bytes per element of the slices that can cross as bfloat16
-        out = {"sh": big * sh, "rest": 4 * (n_flat - sh), "radii": 4 * n_radii}
-        if sh and self.split3:   # 'mid' leaves when the skinning backward is done, 'rest' (deformation parameters + statistics) last
-            out["mid"] = big * self._n_mid()
-            out["rest"] -= 4 * self._n_mid()
-        out["total"] = sum(out.values())
-        return out
-
-    @property
-    def _fold_mean(self):
-        """Flat Adam kernel: the bucket keeps the SUM over the ranks and the kernel reads grad / world (no averaging pass)."""
-        return self.opt_deform is None and self.world > 1
-
-    def _reduce(self):
-        if self.no_collectives:
-            return
-        self.bucket.all_reduce_mean(average=not self._fold_mean)
-        if self.world > 1:
-            dist.all_reduce(self._radii, op=dist.ReduceOp.MAX)
-
-    def _finish_sh(self):
-        """Data-parallel split step: the SH coefficients (first bucket segment, first parameter) can be updated as soon as their
-        all-reduce is done -- while the rest of the bucket is still on the wire."""
-        with torch.no_grad():
-            self.opt_surfels.grad_scale = 1.0 / self.world
-            if self._shard_ok():   # this rank's rows only (their gradient sum arrived by reduce-scatter); _gather_sh_start follows
-                self.opt_surfels.step_slice(0, *self._shard_range())
-            else:
-                self.opt_surfels.step(0, 1)
-
-    def _finish_lanes(self, eager, join=None):
-        """Update behind the k concurrent lanes.  Single GPU: the lanes' buckets are summed by the Adam kernel itself (dgs_adam_step_sum2)
-        and their statistics accumulated one after the other.  Data parallel: the other lanes are folded into lane 0's bucket first
-        (the exchange works on one buffer) -- eagerly, in front of the all-reduce (`eager`; the captured update starts behind it).
-        join: a stream on which the last lane's node-MLP backward is still running (_capture_lanes): the surfel parameters are
-        updated next to it, the stream is joined, then the statistics and the deformation parameters follow."""
-        if self.world > 1:
-            if eager:
-                self._lanes_fold()
-                self._reduce()
-            return self._finish(reduce=False)
-        return self._finish(reduce=False, lanes=self._make_lanes(), join=join)
+    def _accumulate_stats(self, lanes=()):
+        """The densification statistics of the step's view(s) -- bucket tail and radii -- into the surfels' accumulators."""
+        s = self.surfels
+        if self.rasterizer_cls is None and s.get_xyz.is_cuda:
+            from . import _ops
+            for tr in (self,) + tuple(lanes):   # every lane's view statistics (add_densification_stats once per view, gaussian_model.py:484-486)
+                _ops.densify_accumulate(tr.bucket.extra[:self.P], tr.bucket.extra[self.P:2 * self.P], tr._radii[:self.P],
+                                        s.xyz_gradient_accum, s.denom, s.max_radii2D,
+                                        skip=self.opt_surfels.skip if self.opt_deform is None else None)
+        else:
+            s.xyz_gradient_accum.add_(self.bucket.extra[:self.P, None])
+            s.denom.add_(self.bucket.extra[self.P:2 * self.P, None])
+            torch.maximum(s.max_radii2D, self._radii[:self.P], out=s.max_radii2D)
 
     def _finish(self, reduce=True, sh_done=False, mid_done=False, lanes=(), join=None):
+        """What follows a step's backward: the exchange (unless the caller ran it), the gradient scale, the statistics and the Adam
+        update -- torch.optim.Adam on the CPU path (_update_torch), the flat kernel on the HIP path (_update_flat)."""
         s = self.surfels
         with torch.no_grad():
             if reduce:
@@ -1415,451 +550,79 @@ class Trainer:
                 for ln in lanes[1:]:
                     lanes[0].bucket.flat.add_(ln.bucket.flat)
                 self.opt_surfels.grad2 = lanes[0].bucket.flat
-
-            def accumulate():
-                if self.rasterizer_cls is None and s.get_xyz.is_cuda:
-                    from . import _ops
-                    for tr in (self,) + tuple(lanes):   # every lane's view statistics (add_densification_stats once per view, gaussian_model.py:484-486)
-                        _ops.densify_accumulate(tr.bucket.extra[:self.P], tr.bucket.extra[self.P:2 * self.P], tr._radii[:self.P],
-                                                s.xyz_gradient_accum, s.denom, s.max_radii2D,
-                                                skip=self.opt_surfels.skip if self.opt_deform is None else None)
-                else:
-                    s.xyz_gradient_accum.add_(self.bucket.extra[:self.P, None])
-                    s.denom.add_(self.bucket.extra[self.P:2 * self.P, None])
-                    torch.maximum(s.max_radii2D, self._radii[:self.P], out=s.max_radii2D)
-            late = getattr(self, "_late_stats", None)
-            self._late_stats = None
-            adv = not getattr(self, "_guard_early", False)   # the guard kernel of this step was launched by _fwd_bwd already
+            late, self._late_stats = self._late_stats, None
+            adv = not self._guard_early   # the guard kernel of this step was launched by _fwd_bwd already
             self._guard_early = False
             if late is None and join is None:
-                accumulate()
+                self._accumulate_stats(lanes)
             # warm-up: everything up to (not including) `feature` -- unless the motion-mask term is on: its render reaches the mask column
             # of `feature` whether or not the deformation is detached (the hyper columns then see a zero gradient: Adam leaves them)
             feature_idle = self.warmup and not (self._lambda_motion_mask() > 0 and getattr(s, "with_motion_mask", False))
-            n_train = self.n_surfel_params - 1 if feature_idle else None
             if self.opt_deform is not None:
-                if feature_idle:   # torch Adam skips parameters without a gradient, like the reference's detached deformation
-                    s.feature.grad = None
-                if self.lr_schedule:
-                    k = self._steps_done
-                    for g in self.opt_surfels.param_groups:
-                        if g["name"] == "xyz":
-                            g["lr"] = expon_lr(k, self.SCHED_POSITION[0], self.SCHED_POSITION[1], self.SCHED_POSITION[2]) * self._spatial
-                    self.opt_deform.param_groups[0]["lr"] = expon_lr(k, *self.SCHED_DEFORM)
-                self._steps_done += 1
-                self.opt_surfels.step()
-                if not self.warmup:
-                    self.opt_deform.step()
-                elif s.feature.grad is None:   # the flat bucket's view comes back for the next step
-                    s.feature.grad = self.bucket.flat[sum(p.numel() for p in self.bucket.params[:self.n_surfel_params - 1]):][:s.feature.numel()].view_as(s.feature)
-            elif sh_done:
-                first = self.n_surfel_params if mid_done else 1
-                if n_train is None or first < n_train:
-                    self.opt_surfels.step(first, n_train, advance=False)
-            elif self.warmup:
-                self.opt_surfels.step(0, self.n_surfel_params if n_train is None else n_train, advance=adv)   # (never the deformation's parameters)
-                if join is not None:
-                    torch.cuda.current_stream(s.get_xyz.device).wait_stream(join)
-                    accumulate()
-            elif join is not None:
-                # concurrent lanes, single GPU: the surfels while the last lane's node-MLP backward runs on `join`; then everything else
-                self.opt_surfels.step(0, self.n_surfel_params, advance=adv)
-                torch.cuda.current_stream(s.get_xyz.device).wait_stream(join)
-                accumulate()
-                self.opt_surfels.step(self.n_surfel_params, None, advance=False)
-            elif getattr(self.deform, "_join_pending", False):
-                # the node-MLP backward is still running on the side stream: update the surfels, which do
-                # not depend on it, meanwhile; then join and update the deformation parameters
-                self.opt_surfels.step(0, self.n_surfel_params, advance=adv)
-                if late is not None:
-                    self._statistics(*late)
-                    accumulate()
-                    late = None
-                self.deform.join_backward()
-                self.opt_surfels.step(self.n_surfel_params, None, advance=False)
+                self._update_torch(feature_idle)
             else:
-                self.opt_surfels.step(advance=adv)
-            if late is not None:   # (not reached with the current branches: statistics are never dropped)
-                self._statistics(*late)
-                accumulate()
-            # every branch above ran the update over ALL parameters of the bucket (with _finish_sh in the split step)
+                self._update_flat(self.n_surfel_params - 1 if feature_idle else None, adv, late, sh_done, mid_done, lanes, join)
+            # every branch ran the update over ALL parameters of the bucket (with _finish_sh in the split step)
             self._bucket_clean = self.opt_deform is None and bool(getattr(self.opt_surfels, "zero_grads", False))
             if lanes:
                 self.opt_surfels.grad2 = None
 
-    # ---- adaptive density control (train_gui.py:410-423; dgs_amd/densify.py) -----------------------------------------
-    def _moments(self):
-        from . import densify
-        self.settle_shards()
-        return self.opt_surfels.moments if self.opt_deform is None else densify.TorchAdamMoments(self.opt_surfels)
-
-    def densify_and_prune(self, max_grad=0.0002, min_opacity=0.01, extent=1.0, max_screen_size=None, percent_dense=0.01,
-                          noise=None, seed=0):
-        """Clone / split / prune in place (no re-allocation, captured graphs stay valid).  Identical on every rank: the
-        statistics were summed over the ranks by the step, the random draw is seeded by (seed, iteration).
-        Returns (n_cloned, n_split, n_pruned)."""
-        from . import densify
-        self._flush_guard()   # the statistics of a skipped step must be redone before they are used
-        dev = self.surfels.get_xyz.device
-        gen = torch.Generator(device=dev).manual_seed(int(seed) * 1000003 + self.iteration)
-        args = (max_grad, min_opacity, extent, max_screen_size)
-        out = densify.densify_and_prune(self.surfels, self._moments(), *args, percent_dense=percent_dense, noise=noise, generator=gen)
-        if isinstance(out, int):   # slots exhausted: the one case that re-allocates (and re-captures)
-            # a dead slot still costs the per-surfel kernels their share of the step: grow by a quarter, not by multiples
-            self.grow(-(-max(int(1.25 * self.P), self.P + 2 * out) // 1024) * 1024)
-            out = densify.densify_and_prune(self.surfels, self._moments(), *args, percent_dense=percent_dense, noise=noise, generator=gen)
-        return out
-
-    def reset_opacity(self):
-        from . import densify
-        self._flush_guard()
-        densify.reset_opacity(self.surfels, self._moments())
-
-    # ---- storage order of the surfels ------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def reorder_surfels(self, perm):
-        """Permute the surfel slots IN PLACE (new slot i <- old slot perm[i]): parameters, both Adam moments, densification
-        statistics, the alive mask, the neighbour-search seed.  No address changes, so captured graphs stay valid.  The order
-        of the surfels carries no meaning (the reference appends and deletes rows freely); outputs change only through
-        ties between equal-depth surfels (broken by index) and floating-point summation order."""
-        from . import densify
+    def _update_torch(self, feature_idle):
+        """CPU path: the two torch.optim.Adam (surfels | deformation), their schedules set on the host."""
         s = self.surfels
-        perm = perm.to(s.get_xyz.device)
-        assert perm.shape == (self.P,)
-        moments = self._moments()
-        for p in densify.surfel_rows(s).values():
-            p.data.copy_(p.data[perm])
-            for m in moments(p):
-                if m is not None:
-                    m.copy_(m[perm])
-        for name in ("xyz_gradient_accum", "denom", "max_radii2D", "alive"):
-            b = getattr(s, name)
-            b.copy_(b[perm])
-        seed = getattr(self.deform, "_knn_seed", None)
-        if seed is not None and seed.shape[0] == self.P:
-            seed.copy_(seed[perm])
+        if feature_idle:   # torch Adam skips parameters without a gradient, like the reference's detached deformation
+            s.feature.grad = None
+        if self.lr_schedule:
+            k = self._steps_done
+            for g in self.opt_surfels.param_groups:
+                if g["name"] == "xyz":
+                    g["lr"] = expon_lr(k, self.SCHED_POSITION[0], self.SCHED_POSITION[1], self.SCHED_POSITION[2]) * self._spatial
+            self.opt_deform.param_groups[0]["lr"] = expon_lr(k, *self.SCHED_DEFORM)
+        self._steps_done += 1
+        self.opt_surfels.step()
+        if not self.warmup:
+            self.opt_deform.step()
+        elif s.feature.grad is None:   # the flat bucket's view comes back for the next step
+            s.feature.grad = self.bucket.flat[sum(p.numel() for p in self.bucket.params[:self.n_surfel_params - 1]):][:s.feature.numel()].view_as(s.feature)
 
-    @torch.no_grad()
-    def reorder_nodes(self, perm):
-        """Permute the control nodes IN PLACE (new row i <- old row perm[i]): positions + hyper coordinates, radius, weight,
-        their Adam moments; the node indices held in the neighbour-search seed are renamed.  The order of the nodes carries
-        no meaning (the MLP is evaluated per node, skinning sums over a surfel's K neighbours)."""
-        d = self.deform
-        perm = perm.to(d.nodes.device)
-        M = d.nodes.shape[0]
-        assert perm.shape == (M,)
-        for p in (d.nodes, d._node_radius, d._node_weight):
-            p.data.copy_(p.data[perm])
-            for m in self._any_moments(p):
-                if m is not None:
-                    m.copy_(m[perm])
-        seed = getattr(d, "_knn_seed", None)
-        if seed is not None:
-            new_of_old = torch.empty_like(perm)
-            new_of_old[perm] = torch.arange(M, device=perm.device)
-            ok = (seed >= 0) & (seed < M)
-            seed.copy_(torch.where(ok, new_of_old[seed.clamp(0, M - 1)], seed))
-
-    @torch.no_grad()
-    def sort_nodes(self):
-        """Store the control nodes along a Morton curve through their bounding box (padding nodes last): 32 consecutive nodes
-        then fill a small box, which is what lets dgs_knn_refine skip most 32-node blocks for a wave of neighbouring surfels."""
-        d = self.deform
-        x = d.nodes.detach()[:, :3]
-        live = d.live_nodes if hasattr(d, "live_nodes") else torch.ones(x.shape[0], dtype=torch.bool, device=x.device)
-        if callable(live):
-            live = live()
-        if not bool(live.any()):
-            return
-        lo, hi = x[live].min(0).values, x[live].max(0).values
-        q = ((x - lo) / (hi - lo).clamp_min(1e-12) * 1023.0).clamp(0, 1023).to(torch.int64)
-        code = torch.zeros(x.shape[0], dtype=torch.int64, device=x.device)
-        for b in range(10):
-            for c in range(3):
-                code |= ((q[:, c] >> b) & 1) << (3 * b + c)
-        code = torch.where(live, code, torch.full_like(code, 1 << 40))
-        self.reorder_nodes(torch.argsort(code, stable=True))
-
-    @torch.no_grad()
-    def sort_surfels(self):
-        """Store the surfels in the order of their nearest control node (dead slots last).  On MI355X this is what makes the
-        per-surfel kernels of the deformation coherent: the 64 surfels of a wave then read the same one or two node rows
-        (broadcast loads), and the skinning backward can sum a wave's contributions to a node in registers and issue one
-        atomic per (wave, node) (dgs_deform_backward, coherent variant; 97 -> ~20 us at 200 k surfels / 1024 nodes) instead
-        of building 256 LDS tables.  Call after initialisation and after densification; stale order only costs time."""
-        self._flush_guard()
-        s, d = self.surfels, self.deform
-        self.sort_nodes()
-        x, nodes = s.get_xyz.detach(), d.nodes.detach()[:, :3]
-        near = torch.cat([torch.cdist(x[i:i + 16384], nodes).argmin(1) for i in range(0, x.shape[0], 16384)])
-        near = torch.where(s.alive, near, torch.full_like(near, nodes.shape[0]))
-        self.reorder_surfels(torch.argsort(near, stable=True))
-        d.coherent_surfels = bool(x.is_cuda and self.rasterizer_cls is None)
-
-    def set_deterministic(self, on=True):
-        """Bit-reproducible training on the HIP path: every float-atomic sum of the step is replaced by an order-free one -- the
-        backward blend and the skinning backward's node table add 64-bit fixed-point numbers (units of 2^-44) with INTEGER atomics
-        (rasterizer option 7 = 2; dgs_deform_backward accumulate bit 4) instead of float atomics.  Two runs from the same seed then agree
-        bit for bit through densification and opacity resets (tests/test_learning_gpu.py).  Costs ~5-10 % of a step and quantises
-        the blend's partial sums to 6e-14 (a different, equally valid optimisation: kernels_blend.h).  The option lives in the
-        rasterizer context of this trainer's DEVICE; a captured step is re-captured."""
-        from diff_surfel_rasterization import _C
-        on = bool(on)
-        if on == getattr(self, "_deterministic", False):
-            return
-        dev = self.surfels.get_xyz.device
-        assert dev.type == "cuda" and self.rasterizer_cls is None, "deterministic mode is a mode of the HIP path"
-        self._flush_guard()
-        self._deterministic = on
-        # the long-tile path (four workgroups share a tile's list: sums taken stretch-wise, i.e. other roundings than the serial walk) is
-        # given to the first 256 slots of the longest-first dispatch order, and the order of tiles of EQUAL length class in that
-        # order comes from LDS atomics -- which tiles get it is not reproducible once more than 256 qualify.  Serial walks only.
-        # (ADVICE r05: the options live in the device's context, which other code may have configured -- DGS_LONG_TILES=0, a caller's own
-        # deterministic = 1: switching the mode off puts back what switching it on found, not the library's defaults.)
-        if on:
-            self._det_saved = (_C.get_option(7, device=dev), _C.get_option(9, device=dev))
-            _C.set_option(7, 2, device=dev)
-            _C.set_option(9, 0, device=dev)
+    def _update_flat(self, n_train, adv, late, sh_done, mid_done, lanes, join):
+        """HIP path: the flat Adam kernel over the parameter ranges that are still to do, next to whatever backward is still running.
+        n_train: None, or (warm-up) the number of leading parameters that train; adv: this launch also runs the step guard;
+        late: statistics of the view that were held back to go behind the surfel update (_fwd_bwd)."""
+        s, opt, n_surf = self.surfels, self.opt_surfels, self.n_surfel_params
+        if sh_done:
+            first = n_surf if mid_done else 1
+            if n_train is None or first < n_train:
+                opt.step(first, n_train, advance=False)
+        elif self.warmup:
+            opt.step(0, n_surf if n_train is None else n_train, advance=adv)   # (never the deformation's parameters)
+            if join is not None:
+                torch.cuda.current_stream(s.get_xyz.device).wait_stream(join)
+                self._accumulate_stats(lanes)
+        elif join is not None:
+            # concurrent lanes, single GPU: the surfels while the last lane's node-MLP backward runs on `join`; then everything else
+            opt.step(0, n_surf, advance=adv)
+            torch.cuda.current_stream(s.get_xyz.device).wait_stream(join)
+            self._accumulate_stats(lanes)
+            opt.step(n_surf, None, advance=False)
+        elif getattr(self.deform, "_join_pending", False):
+            # the node-MLP backward is still running on the side stream: update the surfels, which do
+            # not depend on it, meanwhile; then join and update the deformation parameters
+            opt.step(0, n_surf, advance=adv)
+            if late is not None:
+                self._statistics(*late)
+                self._accumulate_stats(lanes)
+            self.deform.join_backward()
+            opt.step(n_surf, None, advance=False)
         else:
-            was7, was9 = getattr(self, "_det_saved", (0, 1))
-            _C.set_option(7, was7, device=dev)
-            _C.set_option(9, was9, device=dev)
-        self.deform.fixed_point_tables = on   # the coherent skinning backward's node table: 64-bit fixed-point sums, integer atomics
-        if self._graph:
-            # (the fixed-point rows of the backward are allocated by the eager warm-up steps enable_graph runs before it captures)
-            self._graph = None
-            self.enable_graph(self._capacity)
-
-    def set_regime(self, warmup=None, lambda_normal=None, lambda_dist=None):
-        """Move to another stage of the reference's schedule (see __init__).  The regime is part of the captured step (kernel
-        arguments, which launches exist): a change re-captures, two or three times per run.  Returns whether anything changed."""
-        new = (self.warmup if warmup is None else bool(warmup), self.lambda_normal if lambda_normal is None else float(lambda_normal),
-               self.lambda_dist if lambda_dist is None else float(lambda_dist))
-        if new == (self.warmup, self.lambda_normal, self.lambda_dist):
-            return False
-        self._flush_guard()
-        if self.warmup and not new[0] and self.opt_deform is None:
-            # `feature` and the deformation parameters join the optimisation now: torch.optim.Adam (the reference, train_gui.py:281-285,
-            # 427-432) has skipped them so far, so their own step count starts at 1 -- not at the run's count, which would switch
-            # the bias corrections off for moments that start from zero (3-6 x the learning rate for the first few hundred steps)
-            t_now = float(self.opt_surfels.t.item())
-            self.opt_surfels.set_origin(self.n_surfel_params - 1, None, t_now)
-            for i, steps in getattr(self, "_adopted_steps", {}).items():   # ... or continues where an adopted optimiser stood (adopt_deform_state)
-                self.opt_surfels.set_origin(i, i + 1, t_now - steps)
-        self.warmup, self.lambda_normal, self.lambda_dist = new
-        if self._graph:
-            self._graph = None
-            self.enable_graph(self._capacity)
-        return True
-
-    def oneup_sh_degree(self):
-        """GaussianModel.oneupSHdegree (gaussian_model.py:139-141).  The active degree is an argument of the rasterizer
-        launches, i.e. part of the captured step: re-capture (three times per run at the reference's schedule)."""
-        s = self.surfels
-        if s.active_sh_degree >= s.max_sh_degree:
-            return False
-        self._flush_guard()
-        s.active_sh_degree += 1
-        if self._graph:
-            self._graph = None
-            self.enable_graph(self._capacity)
-        return True
-
-    def grow(self, capacity):
-        """Re-allocate the surfel slots (parameters, gradient bucket, Adam moments, statistics) to `capacity` and re-capture
-        the step's graphs if they were enabled.  Values, moments and the Adam step count carry over."""
-        from . import densify
-        self._flush_guard()
-        s = self.surfels
-        old = s.get_xyz.shape[0]
-        assert capacity > old
-        moments = self._moments()
-        rows = densify.surfel_rows(s)
-        saved = {name: tuple(None if t is None else t.detach().clone() for t in moments(p)) for name, p in rows.items()}
-        deform_saved = [tuple(None if t is None else t.detach().clone() for t in self._param_moments(p)) for p in self.deform.parameters()]
-        if self.opt_deform is None:
-            t_saved = self.opt_surfels.t.clone()
-        else:
-            t_saved = {name: self.opt_surfels.state[p].get("step") for name, p in rows.items() if p in self.opt_surfels.state}
-        fill = {"opacity": densify.DEAD_LOGIT, "scaling": -6.0, "feature": -1e-2}
-        attr = {"xyz": "_xyz", "f_all": "_features", "f_dc": "_features_dc", "f_rest": "_features_rest", "opacity": "_opacity",
-                "scaling": "_scaling", "rotation": "_rotation", "feature": "feature"}
-        n = capacity - old
-        with torch.no_grad():
-            for name, p in rows.items():
-                pad = torch.full((n,) + tuple(p.shape[1:]), fill.get(name, 0.0), dtype=p.dtype, device=p.device)
-                if name == "rotation":
-                    pad[:, 0] = 1
-                setattr(s, attr[name], torch.nn.Parameter(torch.cat((p.detach(), pad)).contiguous()))
-            for name in ("xyz_gradient_accum", "denom", "max_radii2D", "alive"):
-                b = getattr(s, name)
-                setattr(s, name, torch.cat((b, torch.zeros((n,) + tuple(b.shape[1:]), dtype=b.dtype, device=b.device))))
-        for a in ("_half",):
-            if hasattr(self, a):
-                delattr(self, a)
-        self._radii = None
-        self._build_state()
-        moments = self._moments()
-        with torch.no_grad():
-            if self.opt_deform is None:
-                self.opt_surfels.t.copy_(t_saved)
-            for name, p in densify.surfel_rows(s).items():
-                m0, v0 = saved[name]
-                if m0 is None:
-                    continue
-                if self.opt_deform is not None:   # torch Adam creates its state lazily
-                    self.opt_surfels.state[p] = {"step": t_saved[name], "exp_avg": torch.zeros_like(p), "exp_avg_sq": torch.zeros_like(p)}
-                m, v = moments(p)
-                m[:old] = m0
-                v[:old] = v0
-            for p, (m0, v0) in zip(self.deform.parameters(), deform_saved):
-                if m0 is not None and self.opt_deform is None:
-                    m, v = self.opt_surfels.moments(p)
-                    m.copy_(m0)
-                    v.copy_(v0)
-        if self._graph:
-            self._graph = None
-            # the list capacity follows the slot count (the same entries per surfel as before)
-            self._capacity = int(-(-self._capacity * capacity // old))
-            self.enable_graph(self._capacity)
-
-    def densify_nodes(self, max_grad=0.0002):
-        """DeformModel.densify (train_gui.py:413-415, utils/time_utils.py:1286-1385) with the surfels' accumulated view-space
-        gradient.  The node count changes, so the bucket / optimiser are rebuilt (moments and step count carry over) and the
-        step is re-captured; on the HIP path the count is padded to a multiple of 64 (fused MLP kernels) with unreachable
-        nodes.  Returns (n_added, n_pruned) or None if nothing changed."""
-        self._flush_guard()
-        s, d = self.surfels, self.deform
-        fused = self.opt_deform is None
-        with torch.no_grad():
-            x_grad = s.xyz_gradient_accum / s.denom
-            alive = s.alive
-            old = {id(p): tuple(None if t is None else t.detach().clone() for t in self._any_moments(p)) for p in self.bucket.params}
-            t_saved = self.opt_surfels.t.clone() if fused else None
-            # torch Adam counts steps per parameter (a parameter's count starts with its first gradient: the deformation's after the
-            # warm-up); the reference's surgery keeps each state's count, and the re-sized node tensors inherit their predecessors'
-            steps = {}
-            if not fused:
-                for opt in (self.opt_surfels, self.opt_deform):
-                    steps.update({id(p): st["step"].clone() for p, st in opt.state.items() if "step" in st})
-                node_steps = {n: steps.get(id(getattr(d, n))) for n in ("nodes", "_node_radius", "_node_weight")}
-            res = d.densify_nodes(max_grad, s.get_xyz.detach()[alive], x_grad[alive], s.feature.detach()[alive], moments=self._any_moments,
-                                  pad_to=64 if fused else 1)
-            if res is None:
-                return None
-            n_add, n_prune, node_moments = res
-            if not fused:   # torch Adam keyed its state by the replaced parameter objects
-                self.opt_deform = None
-            for a in ("_half",):
-                if hasattr(self, a):
-                    delattr(self, a)
-            self._build_state()
-            new_nodes = {id(getattr(d, n)): mv for n, mv in node_moments.items()}
-            if not fused:
-                steps.update({id(getattr(d, n)): t for n, t in node_steps.items() if t is not None})
-            if fused:
-                self.opt_surfels.t.copy_(t_saved)
-            for p in self.bucket.params:
-                m0, v0 = new_nodes.get(id(p), old.get(id(p), (None, None)))
-                if m0 is None:
-                    continue
-                if not fused:
-                    opt = self.opt_deform if any(p is q for g in self.opt_deform.param_groups for q in g["params"]) else self.opt_surfels
-                    opt.state[p] = {"step": steps.get(id(p), torch.tensor(float(self._steps_done))).clone(), "exp_avg": m0.clone(), "exp_avg_sq": v0.clone()}
-                else:
-                    m, v = self.opt_surfels.moments(p)
-                    m.copy_(m0)
-                    v.copy_(v0)
-        if self._graph:
-            self._graph = None
-            self.enable_graph(self._capacity)
-        return n_add, n_prune
-
-    def _any_moments(self, p):
-        """Adam moments of any parameter of the bucket, whichever optimiser holds it."""
-        if self.opt_deform is None:
-            return self.opt_surfels.moments(p)
-        for opt in (self.opt_surfels, self.opt_deform):
-            st = opt.state.get(p, None)
-            if st:
-                return st["exp_avg"], st["exp_avg_sq"]
-        return None, None
-
-    def _param_moments(self, p):
-        if self.opt_deform is None:
-            return self.opt_surfels.moments(p)
-        return (None, None)
-
-    @torch.no_grad()
-    def hold_surfels(self, nodes=False):
-        """Copies of the per-surfel parameters (nodes=True: of the three node tensors instead) and of their Adam state;
-        release_surfels puts them back.  Around a step: the step trains everything else and gathers the densification statistics, the
-        held parameters stay where they were -- what the reference does to parameters its density control replaces in front of the
-        optimiser's step (dgs_amd.fit.run_iteration)."""
-        from . import densify
-        self.settle_shards()
-        d = self.deform
-        params = [d.nodes, d._node_radius, d._node_weight] if nodes else list(densify.surfel_rows(self.surfels).values())
-        held = []
-        for p in params:
-            m, v = self._any_moments(p)
-            st = self._torch_state(p)
-            held.append((p, p.detach().clone(), None if m is None else m.clone(), None if v is None else v.clone(),
-                         None if not st else st["step"].clone()))
-        return held
-
-    def _torch_state(self, p, pop=False):
-        """torch.optim.Adam's state entry of parameter p (CPU path; the optimisers may have been rebuilt since a hold), or None."""
-        if self.opt_deform is None:
-            return None
-        for opt in (self.opt_surfels, self.opt_deform):
-            if p in opt.state:
-                return opt.state.pop(p) if pop else opt.state[p]
-        return None
-
-    @torch.no_grad()
-    def release_surfels(self, held):
-        self.settle_shards()
-        for p, value, m0, v0, step in held:
-            p.copy_(value)
-            m, v = self._any_moments(p)
-            if m0 is not None:
-                m.copy_(m0)
-                v.copy_(v0)
-            elif m is not None:   # a parameter that saw its first update in this step (torch Adam): back to no state
-                self._torch_state(p, pop=True)
-            if step is not None:
-                self._torch_state(p)["step"].copy_(step)
-
-    @torch.no_grad()
-    def adopt_deform_state(self, adam):
-        """Continue a torch.optim.Adam's state for the deformation parameters: in the reference ONE optimiser of the deformation
-        model runs through the node pre-training stage and the joint stage (scene/deform_model.py:26-33, train_gui.py:590-592 and
-        :429-431), so the joint stage starts with the moments and the per-parameter step counts the first stage left.  `adam`: the
-        optimiser of dgs_amd.node_pretrain.NodePretrainer (same Parameter objects).  Before enable_graph: the step origins are
-        kernel arguments.  Returns the number of parameters whose state was taken over."""
-        n = 0
-        if self.opt_deform is not None:
-            for p, st in adam.state.items():
-                self.opt_deform.state[p] = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in st.items()}
-                n += 1
-            return n
-        assert self._graph is None, "adopt_deform_state before enable_graph"
-        flat = self.opt_surfels
-        for i, p in enumerate(flat.params):
-            st = adam.state.get(p)
-            if not st:
-                continue
-            m, v = flat.moments(p)
-            m.copy_(st["exp_avg"])
-            v.copy_(st["exp_avg_sq"])
-            flat.set_origin(i, i + 1, float(self._steps_done) - float(st["step"]))   # bias corrections continue at step + 1
-            self.__dict__.setdefault("_adopted_steps", {})[i] = float(st["step"])   # (the end of the warm-up re-bases the origins: set_regime)
-            n += 1
-        return n
+            opt.step(advance=adv)
 
     def view_for(self, iteration, j=0):
         """Shared deterministic schedule: step i renders views {(i k + j) world + rank} mod V, j = 0 .. k - 1 (k = views_per_rank)."""
+        return self._scheduled_view(iteration, j)
+
+    def _scheduled_view(self, iteration, j=0):
+        """view_for's default order -- the one the captured step's device-side selection follows, whatever a caller put in view_for's place"""
         return ((iteration * self.views_per_rank + j) * self.world + self.rank) % len(self.cameras)
 
     # ---- k views per rank and step (opt-in lever of the data-parallel step, VERDICT r04 item 4c) -------------------------------
@@ -1867,7 +630,7 @@ class Trainer:
         """The densification statistics of the step's j-th view into side buffers: the kernels of _statistics OVERWRITE the bucket
         tail and the radii; a multi-view step needs the SUM of the gradient norms and visibility counts and the MAX of the radii
         (add_densification_stats once per view, gaussian_model.py:484-486)."""
-        if getattr(self, "_kx", None) is None or self._kx.shape != self.bucket.extra.shape:
+        if self._kx is None or self._kx.shape != self.bucket.extra.shape:
             self._kx = torch.zeros_like(self.bucket.extra)
             self._kr = torch.zeros_like(self._radii)
         if j == 0:
@@ -1881,7 +644,7 @@ class Trainer:
             self._radii.copy_(self._kr)
 
     def _loss_accumulate(self, j, loss):
-        if getattr(self, "_kloss", None) is None:
+        if self._kloss is None:
             self._kloss = torch.zeros(1, dtype=loss.dtype, device=loss.device)
         if j == 0:
             self._kloss.copy_(loss.reshape(1))
@@ -1907,12 +670,6 @@ class Trainer:
             self._loss_accumulate(j, loss)
         return loss
 
-    def _multi_view_step_concurrent(self, views):
-        """Eager twin of _step_lanes: the k views on their lanes' streams, one update."""
-        self._lanes_eager([(self.cameras[v], self.targets[v % len(self.targets)]) for v in views])
-        self._finish_lanes(eager=True)
-        return self._kloss[0].detach().clone()
-
     def _multi_view_step(self, views):
         """One step over k views of this rank: gradients added view by view, then ONE exchange and ONE update -- the neighbour search,
         every all-reduce and the Adam kernels once per k views.  Not split (the SH all-reduce of the split step hides under ONE view's
@@ -1923,7 +680,7 @@ class Trainer:
         return self._kloss[0].detach().clone() if not self._graph else self._kloss
 
     def step(self):
-        guarded = self.opt_deform is None and getattr(self, "_oflag", None) is not None
+        guarded = self.opt_deform is None and self._oflag is not None
         if guarded:
             self._check_guard()
             if not self._graph:   # eager launches read the context's current flag (a captured step has its own baked in)
@@ -1948,73 +705,14 @@ class Trainer:
 
     def _step_views(self, views):
         """A multi-view step (views_per_rank > 1): replay the captured per-view graphs, or run eagerly."""
-        if not self._graph:
-            with trace.stage("dgs.step(%d views)" % len(views)):
-                return self._multi_view_step_concurrent(views) if self._concurrent() else self._multi_view_step(views)
-        if getattr(self, "_glanes", None) is not None and self._gk is None:
-            return self._step_lanes(views)
-        k = self.views_per_rank
-        base = (self.iteration - 1) * k              # what the device's view counter must read in front of this step
-        if self._dev_select:
-            if base != self._vctr_host:
-                self._vctr.fill_(base)
-                self._vctr_host = base
-        for j, v in enumerate(views):
-            if self._dev_select:
-                if v != ((base + j) * self.world + self.rank) % len(self.cameras):
-                    self._vovr.fill_(v)
-                self._vctr_host += 1
-            else:
-                self._scam.load(self._vtab[v])
-            self._gk[0 if j == 0 else (2 if j == k - 1 else 1)].replay()   # first (stores) / middle (adds) / last (adds, closes the statistics)
-        if self._g2 is not None:
-            self._reduce()
-            self._g2.replay()
-        return self._kloss
+        if self._graph:
+            return self._replay_views(views)
+        with trace.stage("dgs.step(%d views)" % len(views)):
+            return self._multi_view_step_concurrent(views) if self._concurrent() else self._multi_view_step(views)
 
     def _step_view(self, v):
         if self._graph:
-            if self._dev_select:
-                # default order: nothing to do on the host -- the graph's first node takes row (counter * world + rank) mod V and counts
-                it = self.iteration - 1            # the iteration this step belongs to (step() has counted it already)
-                if it != self._vctr_host:          # the host's counter was moved (a rewind after skipped steps, a tool): bring the device's along
-                    self._vctr.fill_(it)
-                    self._vctr_host = it
-                if v != (it * self.world + self.rank) % len(self.cameras):   # a view order of the caller's own
-                    self._vovr.fill_(v)
-                self._vctr_host += 1
-            else:
-                self._scam.load(self._vtab[v])   # one 256-byte copy: camera matrices, time, and the pointers of target / ray table
-            if self._g0 is not None:             # sharded SH update: deformation head | wait for the SH rows of the last update | the rest
-                self._g0.replay()
-                self._wait_gather()
-            self._g1.replay()
-            if self._g1b is not None:
-                rwork = self._reduce_radii_start()   # radii + overflow flag (small): first, the SH update's guard reads it
-                work = self._reduce_sh_start()   # runs on the collective's stream while graph 1b replays
-                self._g1b.replay()
-                mid = None
-                if self._g1c is not None:        # third split: per-surfel gradients leave under the node-MLP backward
-                    mid = self._reduce_mid_start()
-                    self._g1c.replay()
-                    rest = self._reduce_tail_start()
-                else:
-                    rest = self._reduce_rest_start()
-                rwork.wait()
-                work.wait()
-                self._g2a.replay()               # SH update while the rest of the bucket is on the wire
-                if self._g0 is not None:
-                    self._gather_sh_start()      # ... and its rows go out behind the rest, under the other updates and the next head
-                if mid is not None:
-                    mid.wait()
-                    self._g2b.replay()
-                for w in rest:
-                    w.wait()
-                self._g2.replay()
-            elif self._g2 is not None:
-                self._reduce()
-                self._g2.replay()
-            return self._sloss
+            return self._replay_view(v)
         cam, gt = self.cameras[v], self.targets[v % len(self.targets)]
         if self._split_ok():
             with trace.stage("dgs.step(split)"):
@@ -2023,37 +721,4 @@ class Trainer:
             loss = self._fwd_bwd(cam, gt)
         with trace.stage("dgs.update"):
             self._finish()
-        return loss
-
-    def _split_step(self, cam, gt):
-        """Data-parallel step, eager: backward half a | SH all-reduce (async) | backward half b | all-reduce of the rest
-        (async) | SH update | update of everything else."""
-        shard = self._shard_ok()
-        head = None
-        if shard:
-            head = self._forward_head(cam)
-            self._wait_gather()
-        loss = self._fwd_bwd_a(cam, gt, head)
-        rwork = self._reduce_radii_start()
-        work = self._reduce_sh_start()
-        mid = None
-        if self.split3:
-            self._fwd_bwd_b1()
-            mid = self._reduce_mid_start()
-            self._fwd_bwd_b2()
-            rest = self._reduce_tail_start()
-        else:
-            self._fwd_bwd_b()
-            rest = self._reduce_rest_start()
-        rwork.wait()
-        work.wait()
-        self._finish_sh()
-        if shard:
-            self._gather_sh_start()
-        if mid is not None:
-            mid.wait()
-            self._finish_mid()
-        for w in rest:
-            w.wait()
-        self._finish(reduce=False, sh_done=True, mid_done=mid is not None)
         return loss
