@@ -2441,8 +2441,10 @@ int dgs_deform_backward(int N, int M, int H, const float* xyz, const float* feat
     const int G = kLbsAttr + H + 2;
     const size_t lds = lbs_bwd_lds_bytes(M, H);
     if (lds > 160 * 1024 || M > 4 * kLbsBwdThreads) return fail(-2, "dgs_deform_backward: node tables do not fit the 160 KB of LDS");
-    if (!scratch || !g_means3D || !g_scales || !g_rotations || !g_opacity || !g_xyz || !g_scaling_raw || !g_rotation_raw ||
-        !g_opacity_raw || !g_feature || !g_nodes || !g_radius_raw || !g_weight_raw || !g_attrs)
+    // an empty surfel set (N == 0: the trainer prunes) has no per-surfel arrays; the node gradients are still produced (all zero)
+    if (!scratch || !g_nodes || !g_radius_raw || !g_weight_raw || !g_attrs ||
+        (N > 0 && (!g_means3D || !g_scales || !g_rotations || !g_opacity || !g_xyz || !g_scaling_raw || !g_rotation_raw ||
+                   !g_opacity_raw || !g_feature)))
         return fail(-1, "dgs_deform_backward: NULL pointer");
     LbsArgs a{N, M, H, feature_stride, xyz, feature, idx, nodes, attrs, mask, 3 + H, node_radius_raw, node_weight_raw};
     AsmArgs s{};
@@ -2460,9 +2462,10 @@ int dgs_deform_backward(int N, int M, int H, const float* xyz, const float* feat
         }
         auto kern = fixed ? (H == 8 ? lbs_bwd_kernel<true, true, 8, true> : lbs_bwd_kernel<true, true, 0, true>)
                           : (H == 8 ? lbs_bwd_kernel<true, true, 8> : lbs_bwd_kernel<true, true, 0>);   // the trainer's hyper_dim, specialised
-        hipLaunchKernelGGL(kern, dim3((N + kCohThreads - 1) / kCohThreads), dim3(kCohThreads), 0, (hipStream_t)stream, a,
-                           (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, g_feature, feature_stride, accumulate & 1,
-                           (float*)scratch, kCohThreads, s);
+        if (N > 0)   // an empty grid is a launch error; the memset above and the reduce below still run
+            hipLaunchKernelGGL(kern, dim3((N + kCohThreads - 1) / kCohThreads), dim3(kCohThreads), 0, (hipStream_t)stream, a,
+                               (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, g_feature, feature_stride, accumulate & 1,
+                               (float*)scratch, kCohThreads, s);
         if (!(accumulate & 8))      // bit 3: the caller reduces the table later (dgs_deform_reduce), e.g. on another stream
             hipLaunchKernelGGL(lbs_reduce_raw_kernel, dim3((M * G + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)scratch, M, H,
                                node_radius_raw, node_weight_raw, g_nodes, g_radius_raw, g_weight_raw, g_attrs, accumulate & 1, 1,
