@@ -1,4 +1,5 @@
-// libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion of rendered depth maps and marching tetrahedra, gfx950.
+// libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion of rendered depth maps, marching tetrahedra and the all-pairs
+// nearest-neighbour search of the mesh metrics, gfx950.
 // Compiled with -ffp-contract=off: every fp32 operation below rounds on its own, which is what makes the result equal to the
 // PyTorch statement of the same arithmetic (dgs_amd/mesh.py) instead of close to it.
 #include <hip/hip_runtime.h>
@@ -258,6 +259,67 @@ __global__ __launch_bounds__(256) void mt_faces_kernel(Grid g, const float* __re
     }
 }
 
+// ---- nearest neighbour ----------------------------------------------------------------------------------------------------------
+// A workgroup owns NN_Q = 256 x NN_K queries (each thread NN_K of them in registers: coordinates, best d2, best index) and one slice
+// of the reference set, which it walks in rounds of NN_T points.  A round is staged into LDS with coalesced loads of the raw
+// [n, 3] floats and de-interleaved on the way (x | y | z planes), so the inner loop reads four points with three 16-byte LDS reads
+// at an address every lane shares: a broadcast, no bank conflict, and one LDS instruction per 16 / 3 query-point pairs of a
+// thread.  Scanning the slice in ascending index with a strict `<` keeps the lowest index among equal distances; across slices the
+// packed (d2 bits, index) minimum does.  Per pair: 3 subtractions, 3 multiplications, 2 additions, compare, 2 selects.
+constexpr int NN_THREADS = 256, NN_K = 4, NN_Q = NN_THREADS * NN_K, NN_T = 1024, NN_CHUNK = 4096;
+
+__global__ __launch_bounds__(NN_THREADS) void nn_search_kernel(long long n_query, const float* __restrict__ query, long long n_ref,
+                                                               const float* __restrict__ ref, long long ref_chunk,
+                                                               unsigned long long* __restrict__ best) {
+    __shared__ __attribute__((aligned(16))) float pts[3 * NN_T];
+    const long long q0 = (long long)blockIdx.x * NN_Q + threadIdx.x;       // this thread's queries: q0 + k * NN_THREADS
+    const long long r_begin = (long long)blockIdx.y * ref_chunk;           // the host clamps ref_chunk to n_ref: no overflow
+    const long long r_end = r_begin + ref_chunk < n_ref ? r_begin + ref_chunk : n_ref;
+    float qx[NN_K], qy[NN_K], qz[NN_K], bd[NN_K];
+    int bi[NN_K];
+#pragma unroll
+    for (int k = 0; k < NN_K; ++k) {
+        const long long q = q0 + (long long)k * NN_THREADS;
+        const bool live = q < n_query;                                     // a thread past the end computes on zeros and stores nothing
+        qx[k] = live ? query[3 * q] : 0.0f, qy[k] = live ? query[3 * q + 1] : 0.0f, qz[k] = live ? query[3 * q + 2] : 0.0f;
+        bd[k] = __builtin_inff(), bi[k] = 0;
+    }
+    auto visit = [&](float x, float y, float z, int r) {
+#pragma unroll
+        for (int k = 0; k < NN_K; ++k) {
+            const float dx = qx[k] - x, dy = qy[k] - y, dz = qz[k] - z;
+            const float d = (dx * dx + dy * dy) + dz * dz;
+            const bool less = d < bd[k];
+            bd[k] = less ? d : bd[k], bi[k] = less ? r : bi[k];
+        }
+    };
+    for (long long rs = r_begin; rs < r_end; rs += NN_T) {
+        const int n = (int)(r_end - rs < NN_T ? r_end - rs : NN_T);       // points of this round: only they are staged and read
+        __syncthreads();                                                   // the previous round's readers are done
+        const float* src = ref + 3 * rs;
+        for (int e = threadIdx.x; e < 3 * n; e += NN_THREADS) {            // 3 (rs + n) <= 3 n_ref: inside the reference array
+            const int p = e / 3;
+            pts[(e - 3 * p) * NN_T + p] = src[e];
+        }
+        __syncthreads();
+        const int base = (int)(rs - r_begin);                              // index within the slice (< n_ref < 2^31)
+        int j = 0;
+        for (; j + 4 <= n; j += 4) {
+            const float4 X = *reinterpret_cast<const float4*>(&pts[j]), Y = *reinterpret_cast<const float4*>(&pts[NN_T + j]),
+                         Z = *reinterpret_cast<const float4*>(&pts[2 * NN_T + j]);
+            visit(X.x, Y.x, Z.x, base + j), visit(X.y, Y.y, Z.y, base + j + 1);
+            visit(X.z, Y.z, Z.z, base + j + 2), visit(X.w, Y.w, Z.w, base + j + 3);
+        }
+        for (; j < n; ++j) visit(pts[j], pts[NN_T + j], pts[2 * NN_T + j], base + j);
+    }
+#pragma unroll
+    for (int k = 0; k < NN_K; ++k) {
+        const long long q = q0 + (long long)k * NN_THREADS;
+        if (q < n_query)
+            atomicMin(&best[q], ((unsigned long long)__float_as_uint(bd[k]) << 32) | (unsigned long long)(unsigned)(r_begin + bi[k]));
+    }
+}
+
 int check_grid(int Nx, int Ny, int Nz, const char* what) {
     if (Nx < 2 || Ny < 2 || Nz < 2) return fail(-1, std::string(what) + ": every grid dimension must be >= 2");
     return 0;
@@ -317,6 +379,31 @@ int dgs_mt_emit(int Nx, int Ny, int Nz, float ox, float oy, float oz, float voxe
     hipLaunchKernelGGL(mt_faces_kernel, dim3(blocks_for(n_cells, 1LL << 31)), dim3(256), 0, (hipStream_t)stream, g, tsdf, n_cells, cells, cell_tris,
                        tri_incl, point_mask, vert_incl, faces);
     return launched("dgs_mt_emit (faces)");
+}
+
+int dgs_nn_search(long long n_query, const float* query, long long n_ref, const float* ref, long long ref_chunk, unsigned long long* best,
+                  void* stream) {
+    if (n_query < 0) return fail(-1, "dgs_nn_search: negative n_query");
+    if (n_ref < 1) return fail(-1, "dgs_nn_search: the reference set must hold at least one point (n_ref >= 1)");
+    if (n_ref >= (1LL << 31)) return fail(-1, "dgs_nn_search: n_ref must be below 2^31 (the index is the low 32 bits of the packed minimum)");
+    if (ref_chunk < 1) return fail(-1, "dgs_nn_search: ref_chunk must be >= 1");
+    if (!ref || (n_query > 0 && (!query || !best))) return fail(-1, "dgs_nn_search: null pointer");
+    if (n_query == 0) return 0;
+    if (ref_chunk > n_ref) ref_chunk = n_ref;
+    const long long slices = (n_ref + ref_chunk - 1) / ref_chunk, blocks = (n_query + NN_Q - 1) / NN_Q;
+    if (slices > 65535) return fail(-1, "dgs_nn_search: more than 65535 slices: raise ref_chunk");
+    if (blocks > 0x7FFFFFFFLL) return fail(-1, "dgs_nn_search: too many queries for one launch");
+    hipError_t e = hipMemsetAsync(best, 0xFF, (size_t)n_query * sizeof(unsigned long long), (hipStream_t)stream);
+    if (e != hipSuccess) return fail(-2, std::string("dgs_nn_search (init): ") + hipGetErrorString(e));
+    hipLaunchKernelGGL(nn_search_kernel, dim3((unsigned)blocks, (unsigned)slices), dim3(NN_THREADS), 0, (hipStream_t)stream, n_query, query, n_ref,
+                       ref, ref_chunk, best);
+    return launched("dgs_nn_search");
+}
+
+int dgs_nn_layout(int out[3]) {
+    if (!out) return fail(-1, "dgs_nn_layout: null pointer");
+    out[0] = NN_Q, out[1] = NN_T, out[2] = NN_CHUNK;
+    return 0;
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
-"""ctypes binding of libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion and marching tetrahedra for gfx950, used by
-dgs_amd.mesh when the volume lives on a HIP device.  CPU tensors use the PyTorch / NumPy statement in dgs_amd.mesh."""
+"""ctypes binding of libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion, marching tetrahedra and the all-pairs nearest-neighbour
+search for gfx950, used by dgs_amd.mesh and dgs_amd.mesh_metrics when the data lives on a HIP device.  CPU tensors use the PyTorch /
+NumPy statements in those modules."""
 import ctypes
 import os
 
@@ -13,7 +14,8 @@ LIB_PATH = os.path.join(_CSRC, "libdgs_mesh_ops.so")
 # and the PyTorch statement of the same arithmetic take the same side of every one of them
 HIPCC_FLAGS = list(_ops.HIPCC_FLAGS) + ["-ffp-contract=off"]
 _lib = None
-_EXPORTS = ("dgs_mesh_ops_abi_version", "dgs_mesh_ops_last_error", "dgs_tsdf_integrate", "dgs_mt_classify", "dgs_mt_emit")
+_EXPORTS = ("dgs_mesh_ops_abi_version", "dgs_mesh_ops_last_error", "dgs_tsdf_integrate", "dgs_mt_classify", "dgs_mt_emit",
+            "dgs_nn_search", "dgs_nn_layout")
 
 
 def _deps():
@@ -54,8 +56,12 @@ def load():
         lib.dgs_mt_classify.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp]
         lib.dgs_mt_emit.restype = ci
         lib.dgs_mt_emit.argtypes = [ci, ci, ci, cf, cf, cf, cf, vp, vp, ll, vp, vp, vp, ll, vp, vp, vp, vp, vp, vp, vp]
-        if lib.dgs_mesh_ops_abi_version() != 1:
-            raise RuntimeError("libdgs_mesh_ops.so ABI version mismatch (want 1, library says %d): rebuild it" % lib.dgs_mesh_ops_abi_version())
+        lib.dgs_nn_search.restype = ci
+        lib.dgs_nn_search.argtypes = [ll, vp, ll, vp, ll, vp, vp]
+        lib.dgs_nn_layout.restype = ci
+        lib.dgs_nn_layout.argtypes = [ctypes.POINTER(ci)]
+        if lib.dgs_mesh_ops_abi_version() != 2:
+            raise RuntimeError("libdgs_mesh_ops.so ABI version mismatch (want 2, library says %d): rebuild it" % lib.dgs_mesh_ops_abi_version())
         _lib = lib
     return _lib
 
@@ -129,3 +135,30 @@ def marching_tetrahedra(dims, origin, voxel, tsdf, weight, color=None):
                                  faces.data_ptr(), _stream(dev))
         _check(lib, rc, "dgs_mt_emit")
     return vertices, faces, colors
+
+
+def nn_layout():
+    """(queries per workgroup, reference points per LDS round, default ref_chunk) of dgs_nn_search."""
+    lib = load()
+    out = (ctypes.c_int * 3)()
+    _check(lib, lib.dgs_nn_layout(out), "dgs_nn_layout")
+    return tuple(int(v) for v in out)
+
+
+def nearest(query, ref, ref_chunk=None):
+    """dgs_nn_search: (d2 [Nq] f32, idx [Nq] int64) of the nearest point of ref [Nr,3] for every point of query [Nq,3]; equal
+    distances go to the lowest index.  The result does not depend on ref_chunk (default: nn_layout()[2])."""
+    lib = load()
+    dev = query.device
+    _f32(query, "query"), _f32(ref, "ref")
+    if ref.device != dev:
+        raise RuntimeError("nearest: ref lives on another device than query")
+    if query.dim() != 2 or query.shape[1] != 3 or ref.dim() != 2 or ref.shape[1] != 3:
+        raise RuntimeError("nearest: query [Nq,3] and ref [Nr,3] are expected")
+    chunk = nn_layout()[2] if ref_chunk is None else int(ref_chunk)
+    best = torch.empty(query.shape[0], dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.dgs_nn_search(query.shape[0], query.data_ptr(), ref.shape[0], ref.data_ptr(), chunk, best.data_ptr(), _stream(dev))
+    _check(lib, rc, "dgs_nn_search")
+    # the packed values are below 2^63 (d2 >= 0: sign bit clear), so the signed shift and mask are the unsigned ones
+    return (best >> 32).to(torch.int32).view(torch.float32), best & 0xFFFFFFFF

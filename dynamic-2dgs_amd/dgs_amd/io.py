@@ -160,6 +160,35 @@ def read_mesh_ply(path):
     return vertices, face["v"].astype(np.int32), colors
 
 
+def read_mesh_obj(path):
+    """(vertices [Nv,3] float32, faces [Nf,3] int32) of a Wavefront OBJ file, by the rules of the reference's ground-truth reader
+    (read_gt_mesh.py: load_obj): a line that starts with `v ` gives a vertex, its first three floats; a line that starts with `f `
+    gives a face, each corner token's integer before the first `/`, 1-based; every other line (vt, vn, comments, groups, materials)
+    is skipped.  Two extensions: a polygon with more than three corners is fan-triangulated -- (c0, c1, c2), (c0, c2, c3), ... --
+    where the reference silently keeps the first three corners, and a negative index counts back from the vertices read so far
+    (-1: the latest), as the format defines it.  An index outside the file's vertices raises ValueError."""
+    verts, faces = [], []
+    with open(path, "r") as f:
+        for n, line in enumerate(f, 1):
+            if line.startswith("v "):
+                verts.append([float(x) for x in line.split()[1:4]])
+            elif line.startswith("f "):
+                corners = []
+                for tok in line.split()[1:]:
+                    i = int(tok.split("/")[0])
+                    corners.append(i - 1 if i > 0 else len(verts) + i)
+                    if i == 0 or corners[-1] < 0:
+                        raise ValueError("%s:%d: vertex index %d out of range" % (path, n, i))
+                if len(corners) < 3:
+                    raise ValueError("%s:%d: a face needs at least three corners" % (path, n))
+                faces.extend([corners[0], corners[k], corners[k + 1]] for k in range(1, len(corners) - 1))
+    v = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
+    fa = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    if fa.size and fa.max() >= v.shape[0]:
+        raise ValueError("%s: a face refers to vertex %d of %d" % (path, int(fa.max()) + 1, v.shape[0]))
+    return v, fa.astype(np.int32)
+
+
 # ---- surfel checkpoint --------------------------------------------------------------------------------------------------
 def surfel_attribute_names(n_dc=3, n_rest=45, n_scale=2, n_rot=4, fea_dim=8):
     """construct_list_of_attributes (gaussian_model.py:229-243)."""

@@ -1,6 +1,7 @@
 /*
- * dgs_mesh_ops.h -- C ABI of the mesh-extraction kernels: depth-map fusion into a truncated signed distance volume and
- * marching tetrahedra over it.  They replace the PyTorch / open3d path of the reference's render_mesh.py:
+ * dgs_mesh_ops.h -- C ABI of the mesh kernels: depth-map fusion into a truncated signed distance volume, marching tetrahedra over
+ * it, and the all-pairs nearest-neighbour search behind the geometry metrics of dgs_amd/mesh_metrics.py.  The first two replace
+ * the PyTorch / open3d path of the reference's render_mesh.py:
  *
  *   dgs_tsdf_integrate          <-  utils/mesh_utils.py:218-266  compute_sdf_perframe + compute_unbounded_tsdf (inv_contraction=None)
  *   dgs_mt_classify / _emit     <-  utils/mesh_utils.py:158-199 / :268-271  volume.extract_triangle_mesh() / marching_cubes_with_contraction
@@ -20,7 +21,7 @@
 extern "C" {
 #endif
 
-#define DGS_MESH_OPS_ABI_VERSION 1
+#define DGS_MESH_OPS_ABI_VERSION 2
 
 int dgs_mesh_ops_abi_version(void);
 const char* dgs_mesh_ops_last_error(void);
@@ -73,6 +74,26 @@ int dgs_mt_emit(int Nx, int Ny, int Nz, float origin_x, float origin_y, float or
                 const float* color, long long n_cells, const long long* cells, const int* cell_tris, const long long* tri_incl,
                 long long n_points, const long long* points, const unsigned char* point_mask, const long long* vert_incl,
                 float* vertices, float* vertex_colors, int* faces, void* stream);
+
+/* Nearest neighbour of every query point in a reference set (brute force, all pairs).  For every query q
+ *   best[q] = min over r in [0, n_ref) of ((unsigned long long)bits(d2(q, r)) << 32 | r)
+ * with d2 = (dx * dx + dy * dy) + dz * dz, dx = q.x - r.x and so on, every operation a separately rounded fp32 one (the library is
+ * compiled with -ffp-contract=off; dgs_amd/mesh_metrics.py: nearest_torch states the same arithmetic in PyTorch).  d2 >= 0, so its
+ * bit pattern orders like its value: the packed minimum is the smallest distance and, among equal distances, the lowest
+ * reference index.  The high word is the fp32 d2, the low word the index; every packed value is below 2^63.
+ *   query [n_query,3], ref [n_ref,3] fp32;   best [n_query] -- set to all-ones on `stream` by this call before the launch
+ *   ref_chunk: the reference set is cut into slices of ref_chunk points (the last one ragged), one grid row per slice; the
+ *     slices meet in `best` through one 64-bit atomic minimum per query and slice, so the result does not depend on ref_chunk
+ *     (values above n_ref mean one slice; dgs_nn_layout gives the default).
+ * Refused with a negative status before any launch: n_ref < 1, n_ref >= 2^31, n_query < 0, ref_chunk < 1, a null pointer with a
+ * non-zero count, more than 65535 slices.  n_query == 0 returns 0 and launches nothing.  Coordinates are expected to be finite (the
+ * Python wrapper refuses others): a slice whose every d2 is NaN or +inf reports (+inf, first index of the slice).  A point of the
+ * last, ragged round or slice is never read past n_ref: tails are index guards, no padded point exists that could win. */
+int dgs_nn_search(long long n_query, const float* query, long long n_ref, const float* ref, long long ref_chunk,
+                  unsigned long long* best, void* stream);
+
+/* out = {queries per workgroup, reference points per LDS round, default ref_chunk}: the sizes at which the kernel changes path. */
+int dgs_nn_layout(int out[3]);
 
 #ifdef __cplusplus
 }
