@@ -584,38 +584,57 @@ def test_unit_gradient_loss_node_matches_two_pass_path(H, W):
     pairs, and (small sizes) against the PyTorch ops.  Depth plane with NaN / +-inf pixels and a background region of zeros."""
     from dgs_amd import losses
     from dgs_amd.cameras import orbit_cameras
+    from dgs_amd.render import camera_rays
+    import loss_ref
     torch.manual_seed(2)
     cam = orbit_cameras(1, W, H)[0].to("cuda")
     gt = torch.rand(3, H, W, device="cuda")
-    vals = {}
     modes = ("unit", "pair") + (("ops",) if H * W < 100_000 else ())
-    for mode in modes:
-        gen = torch.Generator(device="cuda").manual_seed(5)
-        image = (0.6 * torch.rand(3, H, W, device="cuda", generator=gen) + 0.4 * gt).requires_grad_(True)
-        allmap = torch.rand(8, H, W, device="cuda", generator=gen)
-        allmap[5] += 2.0
-        allmap[5, H // 3: H // 3 + 7, : W // 2] = 0.0                 # background: depth 0, degenerate normals (|v| = 0)
-        allmap[5, 5, 7], allmap[5, 9, 3], allmap[5, 11, 11] = float("nan"), float("inf"), float("-inf")
-        allmap[5, 0, 0], allmap[5, H - 1, W - 1] = float("nan"), float("inf")
-        allmap.requires_grad_(True)
-        losses.FUSE_PHOTOMETRIC = mode != "ops"
-        try:
-            loss = losses.training_loss_from_allmap(image, allmap, cam, gt, unit_grad=(mode == "unit"))
-        finally:
-            losses.FUSE_PHOTOMETRIC = True
-        loss.backward(torch.ones((), device="cuda"))
-        vals[mode] = (float(loss), image.grad.clone(), allmap.grad.clone())
-    for other in modes[1:]:
-        la, lb = vals["unit"][0], vals[other][0]
-        if la == la or lb == lb:          # (-inf depth makes the reference's own loss non-finite on some layouts)
-            assert abs(la - lb) <= 1e-5 * abs(lb), (other, la, lb)
-        for a, b in ((vals["unit"][1], vals[other][1]), (vals["unit"][2], vals[other][2])):
-            fin = torch.isfinite(b)
-            assert torch.equal(torch.isfinite(a), fin), other
-            # the depth gradient is a sum of four neighbour terms that cancel at the rim of the degenerate region (values up to
-            # ~170 there): gather order vs atomic order differ by a few ulp of the largest TERM
-            assert float((a[fin] - b[fin]).abs().max()) <= 5e-5 * float(b[fin].abs().max()) + 1e-12, other
-    assert torch.equal(vals["unit"][1], vals["pair"][1])       # the SSIM backward is the same kernel on the same inputs
+    # lambda_dist = 1000 on a uniform-random distortion plane is a loss of ~500 of which the normal term is 0.02: the second pass
+    # (lambda_dist = 0) compares the normal term's value at 1e-5 of itself
+    for lambda_dist in (1000.0, 0.0):
+        vals = {}
+        for mode in modes:
+            gen = torch.Generator(device="cuda").manual_seed(5)
+            image = (0.6 * torch.rand(3, H, W, device="cuda", generator=gen) + 0.4 * gt).requires_grad_(True)
+            allmap = torch.rand(8, H, W, device="cuda", generator=gen)
+            allmap[5] += 2.0
+            allmap[5, H // 3: H // 3 + 7, : W // 2] = 0.0                 # background: depth 0, degenerate normals (|v| = 0)
+            allmap[5, 5, 7], allmap[5, 9, 3], allmap[5, 11, 11] = float("nan"), float("inf"), float("-inf")
+            allmap[5, 0, 0], allmap[5, H - 1, W - 1] = float("nan"), float("inf")
+            allmap.requires_grad_(True)
+            losses.FUSE_PHOTOMETRIC = mode != "ops"
+            try:
+                loss = losses.training_loss_from_allmap(image, allmap, cam, gt, lambda_dist=lambda_dist, unit_grad=(mode == "unit"))
+            finally:
+                losses.FUSE_PHOTOMETRIC = True
+            loss.backward(torch.ones((), device="cuda"))
+            vals[mode] = (float(loss), image.grad.clone(), allmap.grad.clone())
+        # pixels with no degenerate or non-finite pixel within 2 px: F.normalize's eps = 1e-12 branch amplifies the depth gradient at
+        # the rim of the zero block by twelve orders of magnitude, and a tolerance scaled by that maximum checks no ordinary pixel
+        rays_d, rays_o = camera_rays(cam, "cuda")
+        ordinary = loss_ref.ordinary_mask(allmap.detach(), rays_d, rays_o, cam.world_view_transform)
+        assert float(ordinary.float().mean()) > 0.5
+        for other in modes[1:]:
+            la, lb = vals["unit"][0], vals[other][0]
+            print("lambda_dist %g: loss unit %.9g %s %.9g" % (lambda_dist, la, other, lb))
+            if la == la or lb == lb:          # (-inf depth makes the reference's own loss non-finite on some layouts)
+                assert abs(la - lb) <= 1e-5 * abs(lb), (other, la, lb)
+            for a, b in ((vals["unit"][1], vals[other][1]), (vals["unit"][2], vals[other][2])):
+                fin = torch.isfinite(b)
+                assert torch.equal(torch.isfinite(a), fin), other
+                # the depth gradient is a sum of four neighbour terms that cancel at the rim of the degenerate region (values up to
+                # ~170 there): gather order vs atomic order differ by a few ulp of the largest TERM
+                assert float((a[fin] - b[fin]).abs().max()) <= 5e-5 * float(b[fin].abs().max()) + 1e-12, other
+            a5, b5 = vals["unit"][2][5][ordinary], vals[other][2][5][ordinary]
+            assert bool(torch.isfinite(a5).all()) and bool(torch.isfinite(b5).all()), other
+            err, top = float((a5 - b5).abs().max()), float(b5.abs().max())
+            print("lambda_dist %g: ordinary depth gradient unit vs %s: err %.3e, largest ordinary value %.3e" % (lambda_dist, other, err, top))
+            assert err <= 5e-5 * top, (other, err, top)
+        if "ops" in modes:
+            a5, b5 = vals["pair"][2][5][ordinary], vals["ops"][2][5][ordinary]
+            assert float((a5 - b5).abs().max()) <= 5e-5 * float(b5.abs().max()), "pair vs ops"
+        assert torch.equal(vals["unit"][1], vals["pair"][1])       # the SSIM backward is the same kernel on the same inputs
 
 
 def test_stored_gradients_equal_cleared_and_added_ones():
