@@ -1,4 +1,4 @@
-// node_mlp.h -- the control-node deformation MLP of the train step as four gfx950 kernels (included by train_ops.hip).
+// node_mlp.h -- the control-node deformation MLP of the train step as four gfx950 kernels (included by step_kernels.h and train_ops.hip).
 //
 // Replaces, for the 1024 control nodes, DeformNetwork.forward + its autograd (utils/time_utils.py:311-453 of the
 // reference: positional encodings, a 13->256->30 time net, 8 x 256 ReLU layers with a skip concat after layer 4, four
@@ -410,7 +410,7 @@ __global__ void __launch_bounds__(kThreads) mlp_fwd_kernel(FwdArgs a)
 }
 
 // ---- backward chain ---------------------------------------------------------------------------------------------
-// Optional: the reduction of the skinning backward's node table (dgs_deform_reduce, lbs_reduce_raw_kernel) folded into the head of
+// Optional: the reduction of the skinning backward's node table (dgs_deform_reduce, lbs_reduce_raw_kernel of skinning_kernels.h) folded into the head of
 // this kernel.  The table row of a node is [13 attribute gradients | H hyper-coordinate gradients | radius | weight]; a workgroup
 // needs the attribute gradients of its own 8 nodes only, so it reads them from the table, finishes the other columns
 // (exp / sigmoid chain rules of the raw radius and weight), leaves the row zeroed for the next backward and stores the

@@ -1,5 +1,5 @@
 // wave_reduce.h -- sum of 16 per-lane values over the 64 lanes of a gfx950 wave: in registers (permlane swaps + DPP; used by the
-// skinning backward of train_ops.hip) and through the wave's own LDS (the backward blend).
+// skinning backward of skinning_kernels.h) and through the wave's own LDS (the backward blend).
 // (The row-wise sums of the row-per-block backward are in ab/blend_bwd_rows.h.)
 #pragma once
 #include <hip/hip_runtime.h>

@@ -11,20 +11,81 @@ _CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("DGS_TRAIN_OPS_LIB", os.path.join(_CSRC, "libdgs_train_ops.so"))  # override: development A/B builds only
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-slp-vectorize", "-munsafe-fp-atomics"]
 _lib = None
-_EXPORTS = ("dgs_train_ops_abi_version", "dgs_train_ops_last_error", "dgs_ssim_forward", "dgs_ssim_backward", "dgs_knn_points",
-            "dgs_lbs_scratch_bytes", "dgs_lbs_forward", "dgs_lbs_backward", "dgs_adam_plan_bytes", "dgs_adam_plan", "dgs_adam_step",
-            "dgs_regloss_forward", "dgs_regloss_backward", "dgs_mlp_packed_floats", "dgs_mlp_saved_floats", "dgs_mlp_scratch_floats",
-            "dgs_mlp_forward", "dgs_mlp_backward", "dgs_knn_points2", "dgs_deform_forward", "dgs_deform_backward", "dgs_photo_forward",
-            "dgs_photo_backward", "dgs_loss_combine", "dgs_densify_view", "dgs_densify_accumulate", "dgs_knn_refine", "dgs_photo_blocks", "dgs_regloss_blocks", "dgs_regloss_forward_partials", "dgs_adam_step_pattern", "dgs_adam_step_sched", "dgs_lbs_supported", "dgs_regloss_backward_slot",
-            "dgs_step_guard", "dgs_adam_step_guarded", "dgs_adam_step_zero", "dgs_densify_accumulate_guarded", "dgs_regloss_forward_partials_z",
-            "dgs_regloss_fused", "dgs_regloss_fused_blocks", "dgs_photo_backward_combine", "dgs_knn_refine_mode", "dgs_deform_reduce", "dgs_photo_backward_combine_guard",
-            "dgs_adam_step_origin", "dgs_select_row", "dgs_loss_forward_merged", "dgs_mlp_forward_select", "dgs_mlp_backward_reduce",
-            "dgs_adam_step_sum2")
+# name -> (restype, argtypes) of every function include/dgs_train_ops.h declares, grouped like csrc/train_ops.hip.  Written by hand:
+# tests/test_cabi_exports.py compares names and arities with the header.
+_ci, _vp, _cf, _ll, _sz = ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_longlong, ctypes.c_size_t
+_ADAM = [_ci, _vp, _vp, _vp, _vp, _vp, _vp]            # nseg, params, offsets, lrs, lrs2, periods, splits
+_ADAM_SCHED = _ADAM + [_vp, _vp, _cf]                 # ... lrs_final, sched_steps, sched_t0
+_ADAM_TAIL = [_vp, _vp, _vp, _cf, _cf, _cf, _vp]      # exp_avg, exp_avg_sq, step_count, beta1, beta2, eps, plan
+_PHOTO_BWD = [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _cf, _vp, _vp, _vp]   # C, H, W, img, gt, three maps, lambda, g_loss, dL_dimg, gt_slot
+_REG = [_ci, _ci, _vp, _vp, _vp, _vp, _cf, _cf]       # H, W, allmap, rays_d, rays_o, wvt, lambda_normal, lambda_dist
+_KNN2 = [_ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _vp]   # N, M, D1, D2, K, x1, x2, x2_stride, nodes, idx
+_SIGNATURES = {
+    "dgs_train_ops_abi_version": (_ci, []),
+    "dgs_train_ops_last_error": (ctypes.c_char_p, []),
+    # SSIM and the photometric loss
+    "dgs_ssim_forward": (_ci, [_ci, _ci, _ci] + [_vp] * 7),
+    "dgs_ssim_backward": (_ci, [_ci, _ci, _ci] + [_vp] * 8),
+    "dgs_photo_blocks": (_sz, [_ci, _ci, _ci]),
+    "dgs_photo_forward": (_ci, [_ci, _ci, _ci] + [_vp] * 8),
+    "dgs_photo_backward_combine_guard": (_ci, _PHOTO_BWD + [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _ci, _vp]),
+    "dgs_photo_backward_combine": (_ci, _PHOTO_BWD + [_vp, _ll, _vp, _ll, _vp, _vp]),
+    "dgs_photo_backward": (_ci, _PHOTO_BWD + [_vp]),
+    "dgs_loss_combine": (_ci, [_vp, _ll, _vp, _ll, _ll, _cf, _vp, _vp]),
+    # regularisers, merged loss forward
+    "dgs_regloss_blocks": (_sz, [_ci, _ci]),
+    "dgs_regloss_forward": (_ci, _REG + [_vp, _vp]),
+    "dgs_regloss_backward": (_ci, _REG + [_vp, _vp, _vp]),
+    "dgs_regloss_backward_slot": (_ci, _REG + [_vp, _vp, _vp, _ci, _vp]),
+    "dgs_regloss_forward_partials": (_ci, _REG + [_vp, _vp, _vp]),
+    "dgs_regloss_forward_partials_z": (_ci, _REG + [_vp, _vp, _vp, _vp]),
+    "dgs_regloss_fused_blocks": (_sz, [_ci, _ci]),
+    "dgs_regloss_fused": (_ci, _REG + [_vp, _vp, _vp, _vp]),
+    "dgs_loss_forward_merged": (_ci, [_ci, _ci, _ci] + [_vp] * 11 + [_cf, _cf, _vp, _vp, _vp, _vp]),
+    # KNN
+    "dgs_knn_points": (_ci, [_ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp]),
+    "dgs_knn_points2": (_ci, _KNN2 + [_vp, _vp]),
+    "dgs_knn_refine_mode": (_ci, _KNN2 + [_ci, _vp]),
+    "dgs_knn_refine": (_ci, _KNN2 + [_vp]),
+    # control-node skinning
+    "dgs_lbs_supported": (_ci, [_ci, _ci]),
+    "dgs_lbs_scratch_bytes": (_sz, [_ci, _ci]),
+    "dgs_lbs_forward": (_ci, [_ci, _ci, _ci, _vp, _vp, _ci] + [_vp] * 8),
+    "dgs_lbs_backward": (_ci, [_ci, _ci, _ci, _vp, _vp, _ci] + [_vp] * 12),
+    "dgs_deform_forward": (_ci, [_ci, _ci, _ci, _vp, _vp, _ci] + [_vp] * 14),
+    "dgs_deform_backward": (_ci, [_ci, _ci, _ci, _vp, _vp, _ci] + [_vp] * 22 + [_ci, _vp, _vp]),
+    "dgs_deform_reduce": (_ci, [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp]),
+    # flat Adam, step guard, view selection
+    "dgs_adam_plan_bytes": (_sz, [_ll]),
+    "dgs_adam_plan": (_ci, [_ci, _vp, _vp, _vp]),
+    "dgs_adam_step": (_ci, [_ci, _vp, _vp, _vp, _vp] + _ADAM_TAIL + [_vp]),
+    "dgs_adam_step_pattern": (_ci, _ADAM + [_vp] + _ADAM_TAIL + [_vp]),
+    "dgs_adam_step_sched": (_ci, _ADAM_SCHED + [_cf, _vp] + _ADAM_TAIL + [_vp]),
+    "dgs_adam_step_guarded": (_ci, _ADAM_SCHED + [_cf, _vp] + _ADAM_TAIL + [_vp, _vp]),
+    "dgs_adam_step_zero": (_ci, _ADAM_SCHED + [_cf, _vp, _ci] + _ADAM_TAIL + [_vp, _vp]),
+    "dgs_adam_step_origin": (_ci, _ADAM_SCHED + [_vp, _cf, _vp, _ci] + _ADAM_TAIL + [_vp, _vp]),
+    "dgs_adam_step_sum2": (_ci, _ADAM_SCHED + [_vp, _cf, _vp, _vp, _ci] + _ADAM_TAIL + [_vp, _vp]),
+    "dgs_select_row": (_ci, [_vp, _ci, _ci, _vp, _vp, _ci, _ci, _vp, _vp]),
+    "dgs_step_guard": (_ci, [_vp, _vp, _vp, _vp, _ci, _vp, _vp]),
+    # control-node MLP
+    "dgs_mlp_packed_floats": (_sz, []),
+    "dgs_mlp_saved_floats": (_sz, [_ci]),
+    "dgs_mlp_scratch_floats": (_sz, [_ci]),
+    "dgs_mlp_forward": (_ci, [_ci, _vp, _ci, _vp, _ci] + [_vp] * 6),
+    "dgs_mlp_forward_select": (_ci, [_ci, _vp, _ci, _vp, _ci] + [_vp] * 6 + [_ci, _ci, _vp, _vp, _ci, _ci, _vp, _vp]),
+    "dgs_mlp_backward": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp]),
+    "dgs_mlp_backward_reduce": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp]),
+    # densification statistics
+    "dgs_densify_view": (_ci, [_ci] + [_vp] * 6),
+    "dgs_densify_accumulate": (_ci, [_ci] + [_vp] * 7),
+    "dgs_densify_accumulate_guarded": (_ci, [_ci] + [_vp] * 8),
+}
 
 
 def _deps():
     hdr = os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dgs_train_ops.h")
-    return [os.path.join(_CSRC, "train_ops.hip"), hdr, os.path.join(_CSRC, "node_mlp.h"), os.path.join(_CSRC, "wave_reduce.h")]
+    return [hdr] + [os.path.join(_CSRC, n) for n in ("train_ops.hip", "train_common.h", "step_kernels.h", "loss_kernels.h", "knn_kernels.h",
+                                                      "skinning_kernels.h", "node_mlp.h", "wave_reduce.h")]
 
 
 def source_hash():
@@ -40,7 +101,7 @@ def build(force=False, verbose=False):
 
 
 def exported_symbols():
-    return _EXPORTS
+    return tuple(_SIGNATURES)
 
 
 def load():
@@ -51,111 +112,9 @@ def load():
         from diff_surfel_rasterization._C import _refuse_stale
         _refuse_stale(LIB_PATH, source_hash, build)   # never run a binary built from other sources than the tree's
         lib = ctypes.CDLL(LIB_PATH)
-        vp, ci = ctypes.c_void_p, ctypes.c_int
-        lib.dgs_train_ops_abi_version.restype = ci
-        lib.dgs_train_ops_last_error.restype = ctypes.c_char_p
-        lib.dgs_ssim_forward.restype = ci
-        lib.dgs_ssim_forward.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
-        lib.dgs_ssim_backward.restype = ci
-        lib.dgs_ssim_backward.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.dgs_knn_points.restype = ci
-        lib.dgs_knn_points.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp]
-        lib.dgs_lbs_scratch_bytes.restype = ctypes.c_size_t
-        lib.dgs_lbs_scratch_bytes.argtypes = [ci, ci]
-        lib.dgs_lbs_forward.restype = ci
-        lib.dgs_lbs_forward.argtypes = [ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.dgs_lbs_backward.restype = ci
-        lib.dgs_lbs_backward.argtypes = [ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.dgs_regloss_forward.restype = ci
-        lib.dgs_regloss_forward.argtypes = [ci, ci, vp, vp, vp, vp, ctypes.c_float, ctypes.c_float, vp, vp]
-        lib.dgs_regloss_backward.restype = ci
-        lib.dgs_regloss_backward.argtypes = [ci, ci, vp, vp, vp, vp, ctypes.c_float, ctypes.c_float, vp, vp, vp]
-        lib.dgs_adam_plan_bytes.restype = ctypes.c_size_t
-        lib.dgs_adam_plan_bytes.argtypes = [ctypes.c_longlong]
-        lib.dgs_adam_plan.restype = ci
-        lib.dgs_adam_plan.argtypes = [ci, vp, vp, vp]
-        lib.dgs_adam_step.restype = ci
-        lib.dgs_adam_step.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp, vp]
-        lib.dgs_adam_step_pattern.restype = ci
-        lib.dgs_adam_step_pattern.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                              vp, vp]
-        lib.dgs_adam_step_sched.restype = ci
-        lib.dgs_adam_step_sched.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp,
-                                            ctypes.c_float, ctypes.c_float, ctypes.c_float, vp, vp]
-        for f in (lib.dgs_mlp_packed_floats, lib.dgs_mlp_saved_floats, lib.dgs_mlp_scratch_floats):
-            f.restype = ctypes.c_size_t
-        lib.dgs_mlp_packed_floats.argtypes = []
-        lib.dgs_mlp_saved_floats.argtypes = [ci]
-        lib.dgs_mlp_scratch_floats.argtypes = [ci]
-        lib.dgs_mlp_forward.restype = ci
-        lib.dgs_mlp_forward.argtypes = [ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp]
-        lib.dgs_mlp_forward_select.restype = ci
-        lib.dgs_mlp_forward_select.argtypes = [ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, ci, ci, vp, vp]
-        lib.dgs_mlp_backward.restype = ci
-        lib.dgs_mlp_backward.argtypes = [ci, vp, vp, vp, vp, vp, ci, vp]
-        lib.dgs_mlp_backward_reduce.restype = ci
-        lib.dgs_mlp_backward_reduce.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp]
-        lib.dgs_knn_points2.restype = ci
-        lib.dgs_knn_points2.argtypes = [ci, ci, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp]
-        lib.dgs_knn_refine.restype = ci
-        lib.dgs_knn_refine.argtypes = [ci, ci, ci, ci, ci, vp, vp, ci, vp, vp, vp]
-        lib.dgs_deform_reduce.restype = ci
-        lib.dgs_deform_reduce.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp]
-        lib.dgs_knn_refine_mode.restype = ci
-        lib.dgs_knn_refine_mode.argtypes = [ci, ci, ci, ci, ci, vp, vp, ci, vp, vp, ci, vp]
-        lib.dgs_deform_forward.restype = ci
-        lib.dgs_deform_forward.argtypes = [ci, ci, ci, vp, vp, ci] + [vp] * 14
-        lib.dgs_deform_backward.restype = ci
-        lib.dgs_deform_backward.argtypes = [ci, ci, ci, vp, vp, ci] + [vp] * 22 + [ci, vp, vp]
-        lib.dgs_photo_forward.restype = ci
-        lib.dgs_photo_forward.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.dgs_photo_backward.restype = ci
-        lib.dgs_photo_backward.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp, vp]
-        lib.dgs_regloss_backward_slot.restype = ci
-        lib.dgs_regloss_backward_slot.argtypes = [ci, ci, vp, vp, vp, vp, ctypes.c_float, ctypes.c_float, vp, vp, vp, ci, vp]
-        lib.dgs_loss_combine.restype = ci
-        lib.dgs_loss_combine.argtypes = [vp, ctypes.c_longlong, vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_float, vp, vp]
-        lib.dgs_photo_blocks.restype = ctypes.c_size_t
-        lib.dgs_photo_blocks.argtypes = [ci, ci, ci]
-        lib.dgs_regloss_blocks.restype = ctypes.c_size_t
-        lib.dgs_regloss_blocks.argtypes = [ci, ci]
-        lib.dgs_regloss_forward_partials.restype = ci
-        lib.dgs_regloss_forward_partials.argtypes = [ci, ci, vp, vp, vp, vp, ctypes.c_float, ctypes.c_float, vp, vp, vp]
-        lib.dgs_densify_view.restype = ci
-        lib.dgs_densify_view.argtypes = [ci, vp, vp, vp, vp, vp, vp]
-        lib.dgs_densify_accumulate.restype = ci
-        lib.dgs_densify_accumulate.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp]
-        lib.dgs_step_guard.restype = ci
-        lib.dgs_step_guard.argtypes = [vp, vp, vp, vp, ci, vp, vp]
-        lib.dgs_photo_backward_combine.restype = ci
-        lib.dgs_photo_backward_combine.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp, vp, ctypes.c_longlong, vp, ctypes.c_longlong, vp, vp]
-        lib.dgs_photo_backward_combine_guard.restype = ci
-        lib.dgs_photo_backward_combine_guard.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp, vp, ctypes.c_longlong, vp,
-                                                         ctypes.c_longlong, vp, vp, vp, vp, vp, ci, vp]
-        lib.dgs_regloss_fused_blocks.restype = ctypes.c_size_t
-        lib.dgs_regloss_fused_blocks.argtypes = [ci, ci]
-        lib.dgs_regloss_fused.restype = ci
-        lib.dgs_regloss_fused.argtypes = [ci, ci, vp, vp, vp, vp, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp]
-        lib.dgs_loss_forward_merged.restype = ci
-        lib.dgs_loss_forward_merged.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp]
-        lib.dgs_regloss_forward_partials_z.restype = ci
-        lib.dgs_regloss_forward_partials_z.argtypes = [ci, ci, vp, vp, vp, vp, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp]
-        lib.dgs_adam_step_guarded.restype = ci
-        lib.dgs_adam_step_guarded.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp,
-                                              ctypes.c_float, ctypes.c_float, ctypes.c_float, vp, vp, vp]
-        lib.dgs_adam_step_zero.restype = ci
-        lib.dgs_adam_step_zero.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_float, ctypes.c_float, vp, ci, vp, vp, vp,
-                                           ctypes.c_float, ctypes.c_float, ctypes.c_float, vp, vp, vp]
-        lib.dgs_select_row.restype = ci
-        lib.dgs_select_row.argtypes = [vp, ci, ci, vp, vp, ci, ci, vp, vp]
-        lib.dgs_adam_step_origin.restype = ci
-        lib.dgs_adam_step_origin.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_float, vp, ctypes.c_float, vp, ci, vp, vp, vp,
-                                             ctypes.c_float, ctypes.c_float, ctypes.c_float, vp, vp, vp]
-        lib.dgs_densify_accumulate_guarded.restype = ci
-        lib.dgs_densify_accumulate_guarded.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.dgs_adam_step_sum2.restype = ci
-        lib.dgs_adam_step_sum2.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_float, vp, ctypes.c_float, vp, vp, ci, vp, vp, vp,
-                                           ctypes.c_float, ctypes.c_float, ctypes.c_float, vp, vp, vp]
+        for name, (restype, argtypes) in _SIGNATURES.items():
+            f = getattr(lib, name)
+            f.restype, f.argtypes = restype, argtypes
         if lib.dgs_train_ops_abi_version() != 3:
             raise RuntimeError("libdgs_train_ops.so ABI version mismatch (want 3, library says %d): rebuild it" % lib.dgs_train_ops_abi_version())
         _lib = lib
@@ -271,10 +230,7 @@ def fused_lbs(x, feature, idx, ntab, attrs, mask, H):
 
 
 def lbs_supported(M, H):
-    lib = load()
-    lib.dgs_lbs_supported.restype = ctypes.c_int
-    lib.dgs_lbs_supported.argtypes = [ctypes.c_int, ctypes.c_int]
-    return bool(lib.dgs_lbs_supported(int(M), int(H)))
+    return bool(load().dgs_lbs_supported(int(M), int(H)))
 
 
 def select_row(table, counter, override, stride, offset, row_out):
@@ -392,30 +348,36 @@ class FlatAdam:
         return (None if self.skip is None else self.skip.data_ptr(), self.t.data_ptr(), self.status.data_ptr(),
                 None if ring is None else ring.data_ptr(), 0 if ring is None else ring.shape[0])
 
+    def _launch(self, k, segs, origin, grad2, plan, advance, what):
+        """The guard (advance=True) and one dgs_adam_step_sum2 over k segments; segs = (ptrs, off, lr, lr2, period, split, lr_final,
+        sched_steps), grad2 = the optional second gradient buffer."""
+        lib = load()
+        dev = self.grad.device
+        skip = None if self.skip is None else self.skip.data_ptr()
+        with torch.cuda.device(dev):
+            if advance:
+                self.guard()
+            rc = lib.dgs_adam_step_sum2(k, *segs, self.sched_t0, origin, float(self.grad_scale), self.grad.data_ptr(),
+                                        None if grad2 is None else grad2.data_ptr(), 1 if self.zero_grads else 0, self.exp_avg.data_ptr(),
+                                        self.exp_avg_sq.data_ptr(), self.t.data_ptr(), self.betas[0], self.betas[1], self.eps,
+                                        plan.data_ptr(), skip, _stream(dev))
+        _check(lib, rc, what)
+
     @torch.no_grad()
     def step(self, first=0, last=None, advance=True):
         """Adam update of parameters [first, last) (default: all).  advance=False reuses the step count of the previous
         call: a step split over several launches advances the counter on its first launch only."""
-        lib = load()
         dev = self.grad.device
         last = self._n if last is None else last
-        k, ptrs, off, lr, lr2, period, split, lr_final, sched_steps, plan = self._range(first, last)
+        k, *segs, plan = self._range(first, last)
         okey = (first, last)
         cache = self.__dict__.setdefault("_origin_slices", {})
         origin = cache.get(okey)
         if origin is None:   # (one ctypes array per (first, last), like _range: an eager step makes no Python list of all origins)
             origin = cache[okey] = (ctypes.c_float * k)(*[self._origin[i] for i in range(first, last)])
-        skip = None if self.skip is None else self.skip.data_ptr()
-        with torch.cuda.device(dev):
-            if advance:
-                self.guard()
-            g2 = self.grad2
-            assert g2 is None or (g2.numel() >= self.grad.numel() and g2.is_contiguous() and g2.dtype == torch.float32 and g2.device == dev)
-            rc = lib.dgs_adam_step_sum2(k, ptrs, off, lr, lr2, period, split, lr_final, sched_steps, self.sched_t0, origin, float(self.grad_scale),
-                                      self.grad.data_ptr(), None if g2 is None else g2.data_ptr(), 1 if self.zero_grads else 0,
-                                      self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.t.data_ptr(), self.betas[0],
-                                      self.betas[1], self.eps, plan.data_ptr(), skip, _stream(dev))
-        _check(lib, rc, "dgs_adam_step")
+        g2 = self.grad2
+        assert g2 is None or (g2.numel() >= self.grad.numel() and g2.is_contiguous() and g2.dtype == torch.float32 and g2.device == dev)
+        self._launch(k, segs, origin, g2, plan, advance, "dgs_adam_step")
 
     @torch.no_grad()
     def step_slice(self, index, lo, hi, advance=True):
@@ -438,21 +400,13 @@ class FlatAdam:
             self._plans[key] = ((ctypes.c_void_p * 1)(self.params[index].data_ptr() + 4 * lo), off, one(self._lr, ctypes.c_float),
                                 one(self._lr2, ctypes.c_float), one(self._period, ctypes.c_int), one(self._split, ctypes.c_int),
                                 one(self._lr_final, ctypes.c_float), one(self._sched_steps, ctypes.c_float), plan)
-        ptrs, off, lr, lr2, period, split, lr_final, sched_steps, plan = self._plans[key]
+        *segs, plan = self._plans[key]
         if hi == lo:
             if advance:
                 self.guard()
             return
         origin = (ctypes.c_float * 1)(self._origin[index])
-        skip = None if self.skip is None else self.skip.data_ptr()
-        with torch.cuda.device(dev):
-            if advance:
-                self.guard()
-            rc = lib.dgs_adam_step_origin(1, ptrs, off, lr, lr2, period, split, lr_final, sched_steps, self.sched_t0, origin, float(self.grad_scale),
-                                        self.grad.data_ptr(), 1 if self.zero_grads else 0,
-                                        self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.t.data_ptr(), self.betas[0],
-                                        self.betas[1], self.eps, plan.data_ptr(), skip, _stream(dev))
-        _check(lib, rc, "dgs_adam_step (slice)")
+        self._launch(1, segs, origin, None, plan, advance, "dgs_adam_step (slice)")   # grad2 stays out of a slice update
 
 
 class _FusedRegLoss(torch.autograd.Function):

@@ -36,7 +36,7 @@ def _blur(x, w1d, channel):
 
 def ssim(img1, img2, window_size=11):
     """Mean SSIM of two [C,H,W] (or [B,C,H,W]) images.  HIP tensors go through the fused gfx950 kernel
-    (csrc/train_ops.hip), CPU tensors through the PyTorch formulation below (same arithmetic)."""
+    (csrc/loss_kernels.h), CPU tensors through the PyTorch formulation below (same arithmetic)."""
     if img1.is_cuda and img1.dim() == 3 and window_size == 11 and img1.dtype == torch.float32:
         from . import _ops
         return _ops.fused_ssim(img1, img2)
@@ -74,13 +74,13 @@ def training_loss(pkg, gt_image, lambda_dssim=0.2, lambda_normal=0.02, lambda_di
     return loss_img + normal_loss + dist_loss
 
 
-FUSE_PHOTOMETRIC = True  # L1 + D-SSIM + regularisers as one autograd node (csrc/train_ops.hip); False: separate ops
+FUSE_PHOTOMETRIC = True  # L1 + D-SSIM + regularisers as one autograd node (csrc/loss_kernels.h); False: separate ops
 
 
 def training_loss_from_allmap(image, allmap, cam, gt_image, lambda_dssim=0.2, lambda_normal=0.02, lambda_dist=1000.0, unit_grad=False, guard=None):
     """Same value and gradients as training_loss(render(...), gt) but computed from the rasterizer outputs directly:
     on a HIP device the allmap post-processing (normal rotation, depth -> points -> normals) and the two regularisers
-    are one fused kernel per direction (csrc/train_ops.hip) instead of ~100 elementwise launches."""
+    are one fused kernel per direction (csrc/loss_kernels.h) instead of ~100 elementwise launches."""
     from . import _ops
     from .render import camera_rays
     rays_d, rays_o = camera_rays(cam, image.device)

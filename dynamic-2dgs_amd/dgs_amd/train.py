@@ -224,7 +224,7 @@ class Trainer(GuardMixin, CaptureMixin, ExchangeMixin, LanesMixin, SurgeryMixin)
             # ... and its backward is launched by _fwd_bwd on a side stream, next to the surfels' Adam update
             deform.defer_mlp_backward = fused_adam
         if fused_adam:
-            # HIP device: one flat Adam launch for surfels + deformation (csrc/train_ops.hip); step counter on the device
+            # HIP device: one flat Adam launch for surfels + deformation (csrc/step_kernels.h); step counter on the device
             from . import _ops
             lr_of = {id(p): g['lr'] for g in groups + deform_groups for p in g['params']}
             pat_of = {id(p): g['pattern'] for g in groups for p in g['params'] if 'pattern' in g}

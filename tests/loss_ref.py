@@ -1,4 +1,4 @@
-"""Plain-PyTorch reference of the training-loss kernels of csrc/train_ops.hip (ssim_fwd_kernel / ssim_bwd_kernel, regloss_fwd_kernel /
+"""Plain-PyTorch reference of the training-loss kernels of csrc/loss_kernels.h (ssim_fwd_kernel / ssim_bwd_kernel, regloss_fwd_kernel /
 regloss_bwd_kernel, regloss_fused_kernel, loss_fwd_merged_kernel, loss_combine_kernel), written from the formulas of
 include/dgs_train_ops.h and dgs_amd/losses.py, at any floating-point precision: float64 is the reference of
 tests/test_loss_fp64_gpu.py, float32 its yardstick (what a straight float32 evaluation of the same formulas loses against float64).

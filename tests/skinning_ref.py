@@ -1,5 +1,5 @@
 """Plain-PyTorch reference of the control-node skinning kernels (lbs_fwd_kernel / lbs_bwd_kernel and their reductions in
-csrc/train_ops.hip), written from the formulas of include/dgs_train_ops.h, for any hyper dimension 0 <= H <= 13 and at any
+csrc/skinning_kernels.h), written from the formulas of include/dgs_train_ops.h, for any hyper dimension 0 <= H <= 13 and at any
 floating-point precision: float64 is the reference of tests/test_skinning_fp64_gpu.py, float32 its yardstick (what a straight
 float32 evaluation of the same formulas loses against float64).  tests/test_skinning_ref_cpu.py ties it to ControlNodes.forward,
 which the goldens pin against the original project.  A helper module: no tests in here."""

@@ -42,3 +42,62 @@ def test_python_bindings_list_matches_headers():
     from diff_surfel_rasterization import _C
     assert sorted(_ops.exported_symbols()) == declared_functions("dgs_train_ops.h")
     assert set(declared_functions("dgs_surfel_rasterizer.h")) <= set(_C.exported_symbols()) | {"dgs_alloc_fn"}
+
+
+def _ops_module():
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "dynamic-2dgs_amd"))
+    from dgs_amd import _ops
+    return _ops
+
+
+def test_train_ops_deps_are_the_include_closure():
+    """_ops._deps() (what the stale-binary hash covers) is exactly the set of files train_ops.hip reaches through relative
+    #include "..." lines: a header missing from the list would hide kernel edits from the hash, a listed header that is no
+    longer included fails too."""
+    todo, seen = [os.path.join(CSRC, "train_ops.hip")], set()
+    while todo:
+        path = os.path.normpath(todo.pop())
+        if path in seen:
+            continue
+        seen.add(path)
+        for inc in re.findall(r'^\s*#\s*include\s*"([^"]+)"', open(path).read(), flags=re.M):
+            todo.append(os.path.join(os.path.dirname(path), inc))
+    deps = [os.path.normpath(p) for p in _ops_module()._deps()]
+    assert len(deps) == len(set(deps))
+    assert set(deps) == seen, (sorted(set(deps) - seen), sorted(seen - set(deps)))
+
+
+def _prototypes(header):
+    """{name: (return type, number of parameters)} of the header's dgs_* prototypes."""
+    text = open(os.path.join(ROOT, "include", header)).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    out = {}
+    for m in re.finditer(r"([A-Za-z_][A-Za-z0-9_ ]*?[\s\*]+)(dgs_[a-z0-9_]+)\s*\(", text):
+        depth, commas, i = 1, 0, m.end()
+        while depth:
+            c = text[i]
+            depth += (c == "(") - (c == ")")
+            commas += c == "," and depth == 1
+            i += 1
+        args = text[m.end():i - 1].strip()
+        assert text[i:].lstrip().startswith(";"), m.group(2)
+        out[m.group(2)] = (" ".join(m.group(1).replace("*", " * ").split()), 0 if args in ("", "void") else commas + 1)
+    return out
+
+
+def test_binding_table_matches_header_arity():
+    """Every prototype of dgs_train_ops.h has a table entry with as many argtypes as the prototype has parameters and the restype of
+    its return type: ctypes passes a call of the wrong arity without complaint."""
+    table = _ops_module()._SIGNATURES
+    protos = _prototypes("dgs_train_ops.h")
+    assert sorted(protos) == declared_functions("dgs_train_ops.h")
+    restypes = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p}
+    wrong = []
+    for name, (ret, nargs) in sorted(protos.items()):
+        restype, argtypes = table[name]
+        if restype is not restypes[ret] or len(argtypes) != nargs:
+            wrong.append((name, ret, nargs, restype, len(argtypes)))
+    assert not wrong, wrong

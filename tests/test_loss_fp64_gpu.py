@@ -1,4 +1,4 @@
-"""-m gpu: the training-loss kernels of csrc/train_ops.hip (ssim_fwd_kernel, ssim_bwd_kernel and the combine rider in its last
+"""-m gpu: the training-loss kernels of csrc/loss_kernels.h (ssim_fwd_kernel, ssim_bwd_kernel and the combine rider in its last
 workgroup, regloss_fwd_kernel / regloss_bwd_kernel, regloss_fused_kernel, loss_fwd_merged_kernel, loss_combine_kernel) against the
 float64 reference of tests/loss_ref.py, per output, per REGION of the image and per term of the loss.
 

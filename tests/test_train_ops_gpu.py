@@ -1,5 +1,5 @@
-"""-m gpu: the fused SSIM and KNN kernels (csrc/train_ops.hip) against the PyTorch formulations they replace
-(which tests/ verify on the CPU against the reference's formula / brute force)."""
+"""-m gpu: the fused SSIM and KNN kernels (csrc/loss_kernels.h, csrc/knn_kernels.h; entry points in csrc/train_ops.hip)
+against the PyTorch formulations they replace (which tests/ verify on the CPU against the reference's formula / brute force)."""
 import numpy as np
 import pytest
 import torch
