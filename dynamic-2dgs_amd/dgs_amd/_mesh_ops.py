@@ -1,5 +1,5 @@
 """ctypes binding of libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion, marching tetrahedra and the all-pairs nearest-neighbour
-search for gfx950, used by dgs_amd.mesh and dgs_amd.mesh_metrics when the data lives on a HIP device.  CPU tensors use the PyTorch /
+and closest-triangle searches for gfx950, used by dgs_amd.mesh and dgs_amd.mesh_metrics when the data lives on a HIP device.  CPU tensors use the PyTorch /
 NumPy statements in those modules."""
 import ctypes
 import os
@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_CSRC, "libdgs_mesh_ops.so")
 HIPCC_FLAGS = list(_ops.HIPCC_FLAGS) + ["-ffp-contract=off"]
 _lib = None
 _EXPORTS = ("dgs_mesh_ops_abi_version", "dgs_mesh_ops_last_error", "dgs_tsdf_integrate", "dgs_mt_classify", "dgs_mt_emit",
-            "dgs_nn_search", "dgs_nn_layout")
+            "dgs_nn_search", "dgs_nn_layout", "dgs_tri_search", "dgs_tri_layout")
 
 
 def _deps():
@@ -60,6 +60,10 @@ def load():
         lib.dgs_nn_search.argtypes = [ll, vp, ll, vp, ll, vp, vp]
         lib.dgs_nn_layout.restype = ci
         lib.dgs_nn_layout.argtypes = [ctypes.POINTER(ci)]
+        lib.dgs_tri_search.restype = ci
+        lib.dgs_tri_search.argtypes = [ll, vp, ll, vp, ll, vp, vp]
+        lib.dgs_tri_layout.restype = ci
+        lib.dgs_tri_layout.argtypes = [ctypes.POINTER(ci)]
         if lib.dgs_mesh_ops_abi_version() != 2:
             raise RuntimeError("libdgs_mesh_ops.so ABI version mismatch (want 2, library says %d): rebuild it" % lib.dgs_mesh_ops_abi_version())
         _lib = lib
@@ -160,5 +164,34 @@ def nearest(query, ref, ref_chunk=None):
     with torch.cuda.device(dev):
         rc = lib.dgs_nn_search(query.shape[0], query.data_ptr(), ref.shape[0], ref.data_ptr(), chunk, best.data_ptr(), _stream(dev))
     _check(lib, rc, "dgs_nn_search")
+    # the packed values are below 2^63 (d2 >= 0: sign bit clear), so the signed shift and mask are the unsigned ones
+    return (best >> 32).to(torch.int32).view(torch.float32), best & 0xFFFFFFFF
+
+
+def tri_layout():
+    """(queries per workgroup, triangles per LDS round, default tri_chunk, floats per table row) of dgs_tri_search."""
+    lib = load()
+    out = (ctypes.c_int * 4)()
+    _check(lib, lib.dgs_tri_layout(out), "dgs_tri_layout")
+    return tuple(int(v) for v in out)
+
+
+def closest_face(points, table, tri_chunk=None):
+    """dgs_tri_search: (d2 [Nq] f32, face [Nq] int64) of the closest triangle of table [Nf,row] (mesh_metrics.triangle_table) for
+    every point of points [Nq,3]; equal distances go to the lowest face.  The result does not depend on tri_chunk (default:
+    tri_layout()[2])."""
+    lib = load()
+    dev = points.device
+    _f32(points, "points"), _f32(table, "table")
+    if table.device != dev:
+        raise RuntimeError("closest_face: table lives on another device than points")
+    layout = tri_layout()
+    if points.dim() != 2 or points.shape[1] != 3 or table.dim() != 2 or table.shape[1] != layout[3]:
+        raise RuntimeError("closest_face: points [Nq,3] and table [Nf,%d] are expected" % layout[3])
+    chunk = layout[2] if tri_chunk is None else int(tri_chunk)
+    best = torch.empty(points.shape[0], dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.dgs_tri_search(points.shape[0], points.data_ptr(), table.shape[0], table.data_ptr(), chunk, best.data_ptr(), _stream(dev))
+    _check(lib, rc, "dgs_tri_search")
     # the packed values are below 2^63 (d2 >= 0: sign bit clear), so the signed shift and mask are the unsigned ones
     return (best >> 32).to(torch.int32).view(torch.float32), best & 0xFFFFFFFF

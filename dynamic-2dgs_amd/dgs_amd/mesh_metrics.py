@@ -1,10 +1,13 @@
 """Geometry metrics between two triangle meshes: how far the surface written by dgs_amd.mesh is from a ground-truth surface.  The
 reference's meshes are judged on the DG-Mesh benchmark by the Chamfer distance to a ground-truth mesh per frame (its tree carries
 the reader of those, read_gt_mesh.py: load_obj); this module samples both surfaces, finds every sample's nearest neighbour in the
-other set and reports the directed means, Chamfer distance, precision / recall / F-score and normal consistency.
+other set and reports the directed means, Chamfer distance, precision / recall / F-score and normal consistency.  With
+mode="surface" a sample's distance is the exact one to the other SURFACE (the minimum over its triangles), which has no sampling floor.
 
   nearest          all-pairs nearest neighbour; HIP device: dgs_nn_search of libdgs_mesh_ops.so (include/dgs_mesh_ops.h states the
                    arithmetic and the tie rule); CPU tensors: nearest_torch, the PyTorch statement of the same arithmetic
+  closest_face     exact point-to-triangle distance to the closest face of a mesh; HIP device: dgs_tri_search over the rows of
+                   triangle_table; CPU tensors: closest_face_torch, the PyTorch statement of the same arithmetic
   sample_surface   area-weighted uniform samples of a mesh, the same points on every device
   mesh_distance    the metrics of one pair of meshes
   read_mesh        .ply (io.read_mesh_ply) or .obj (io.read_mesh_obj)
@@ -20,6 +23,8 @@ import numpy as np
 import torch
 
 _PAIR_BUDGET = 1 << 24   # elements of one [chunk, Nr] intermediate of nearest_torch
+_TRI_LIVE = 16           # closest_face_torch keeps about twenty [chunk, Nf] intermediates alive: its chunk is that much smaller
+TRI_VALUES, TRI_ROW = 34, 36   # values of a triangle_table row, floats of a row (padded to 16 bytes; = dgs_tri_layout()[3])
 
 
 # ---- nearest neighbour ----------------------------------------------------------------------------------------------------------
@@ -47,11 +52,11 @@ def nearest_torch(query, ref, chunk=None):
     return d2, idx
 
 
-def _points(x, what):
+def _points(x, what, who="nearest"):
     if not torch.is_tensor(x) or x.dim() != 2 or x.shape[1] != 3 or not x.is_floating_point():
-        raise ValueError("nearest: %s must be a floating-point tensor [N,3]" % what)
+        raise ValueError("%s: %s must be a floating-point tensor [N,3]" % (who, what))
     if not bool(torch.isfinite(x).all()):
-        raise ValueError("nearest: %s holds non-finite coordinates" % what)
+        raise ValueError("%s: %s holds non-finite coordinates" % (who, what))
     return x
 
 
@@ -70,6 +75,105 @@ def nearest(query, ref, ref_chunk=None):
         return nearest_torch(query, ref)
     from . import _mesh_ops
     return _mesh_ops.nearest(query.float().contiguous(), ref.float().contiguous(), ref_chunk)
+
+
+# ---- closest face ---------------------------------------------------------------------------------------------------------------
+def _dot(a, b):
+    return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]          # (x x' + y y') + z z', one rounding per operation
+
+
+def _cross(a, b):
+    return (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
+
+
+def _safe_reciprocal(x):
+    """1 / x where x > 0 and the quotient is finite, else 0."""
+    r = 1.0 / x
+    return torch.where((x > 0) & torch.isfinite(r), r, torch.zeros_like(r))
+
+
+@torch.no_grad()
+def triangle_table(vertices, faces):
+    """[Nf, TRI_ROW] in the dtype and on the device of `vertices`: per face with corners A, B, C the row A, B, C, e0 = B - A,
+    e1 = C - B, e2 = A - C, n = cross(e0, C - A), m_k = cross(n, e_k), r_k = 1 / dot(e_k, e_k), rn = 1 / dot(n, n) (0 where the
+    dot product is not positive or the quotient not finite) and two zeros of padding -- the table of dgs_tri_search
+    (include/dgs_mesh_ops.h), elementwise operations only, every one rounded on its own."""
+    v = vertices.detach().reshape(-1, 3)
+    f = faces.detach().reshape(-1, 3).long().to(v.device)
+    xyz = lambda p: (p[:, 0], p[:, 1], p[:, 2])
+    a, b, c = xyz(v[f[:, 0]]), xyz(v[f[:, 1]]), xyz(v[f[:, 2]])
+    sub = lambda p, q: (p[0] - q[0], p[1] - q[1], p[2] - q[2])
+    e0, e1, e2 = sub(b, a), sub(c, b), sub(a, c)
+    n = _cross(e0, sub(c, a))
+    m0, m1, m2 = _cross(n, e0), _cross(n, e1), _cross(n, e2)
+    tail = (_safe_reciprocal(_dot(e0, e0)), _safe_reciprocal(_dot(e1, e1)), _safe_reciprocal(_dot(e2, e2)), _safe_reciprocal(_dot(n, n)))
+    zero = torch.zeros_like(tail[0])
+    return torch.stack(a + b + c + e0 + e1 + e2 + n + m0 + m1 + m2 + tail + (zero,) * (TRI_ROW - TRI_VALUES), dim=1).contiguous()
+
+
+def _pair_d2(points, col):
+    """[Nq, Nf] squared distances of every (point, row) pair; col = the table's 34 value columns as [34, 1, Nf]."""
+    tri = lambda i: (col[i], col[i + 1], col[i + 2])
+    p = (points[:, 0:1], points[:, 1:2], points[:, 2:3])
+    best, inside, w0 = None, col[33] > 0, None
+    for k in range(3):
+        o, e = tri(3 * k), tri(9 + 3 * k)
+        w = (p[0] - o[0], p[1] - o[1], p[2] - o[2])
+        t = (_dot(w, e) * col[30 + k]).clamp(0, 1)
+        c = (w[0] - t * e[0], w[1] - t * e[1], w[2] - t * e[2])
+        sk = _dot(c, c)
+        best = sk if best is None else torch.minimum(best, sk)
+        inside = inside & (_dot(w, tri(21 + 3 * k)) >= 0)
+        w0 = w if k == 0 else w0
+    h = _dot(w0, tri(18))
+    return torch.where(inside, torch.minimum(h * h * col[33], best), best)
+
+
+def closest_face_torch(points, table, chunk=None):
+    """The arithmetic of dgs_tri_search in PyTorch, in the dtype and on the device of the tensors, chunked over the queries.  Per
+    pair (P, row):  w_k = P - O_k;  t = clamp(dot(w_k, e_k) * r_k, 0, 1);  c = w_k - t e_k;  s_k = dot(c, c);  best = min(s_0, s_1,
+    s_2);  inside = (dot(w_k, m_k) >= 0 for all k) & (rn > 0);  h = dot(w_0, n);  pl = (h h) rn;  d2 = inside ? min(pl, best) : best
+    -- elementwise operations, one rounding each (_pair_d2); then the minimum over the faces and, among equal distances, the
+    lowest face, written out.  -> (d2 [Nq], face [Nq] int64).  The CPU path, the comparator of the GPU tests and the baseline of
+    tools/mesh_surface_timing.py."""
+    nq, nf = points.shape[0], table.shape[0]
+    if nf < 1:
+        raise ValueError("closest_face: the mesh has no faces")
+    if chunk is None:
+        chunk = max(1, _PAIR_BUDGET // _TRI_LIVE // nf)
+    col = table[:, :TRI_VALUES].t().contiguous().unsqueeze(1)               # [34, 1, Nf]: col[i] broadcasts against [chunk, 1]
+    index = torch.arange(nf, dtype=torch.int64, device=table.device).unsqueeze(0)
+    d2 = torch.empty(nq, dtype=points.dtype, device=points.device)
+    face = torch.empty(nq, dtype=torch.int64, device=points.device)
+    for s in range(0, nq, chunk):
+        d = _pair_d2(points[s:s + chunk], col)
+        m = d.min(dim=1, keepdim=True).values
+        d2[s:s + chunk] = m[:, 0]
+        face[s:s + chunk] = torch.where(d == m, index, nf).min(dim=1).values
+    return d2, face
+
+
+@torch.no_grad()
+def closest_face(points, vertices, faces, face_chunk=None):
+    """(d2 [Nq], face [Nq] int64): squared distance from every point of points [Nq,3] to the surface of the mesh (vertices [Nv,3],
+    faces [Nf,3]) -- the exact point-to-triangle distance, minimised over the faces -- and the face that attains it; equal
+    distances go to the lowest face.  Degenerate faces are legal: they act as their segments or their point.  HIP tensors (fp32):
+    the kernel, face_chunk = its slice of the faces per workgroup (the result does not depend on it); CPU tensors:
+    closest_face_torch in the dtype of `points`.  Nf = 0, non-finite coordinates and mixed devices raise ValueError before
+    anything is launched."""
+    _points(points, "points", "closest_face"), _points(vertices, "vertices", "closest_face")
+    if not torch.is_tensor(faces) or faces.dim() != 2 or faces.shape[1] != 3 or faces.is_floating_point():
+        raise ValueError("closest_face: faces must be an integer tensor [Nf,3]")
+    if faces.shape[0] < 1:
+        raise ValueError("closest_face: the mesh has no faces")
+    if points.device != vertices.device or points.device != faces.device:
+        raise ValueError("closest_face: points, vertices and faces live on different devices")
+    if int(faces.min()) < 0 or int(faces.max()) >= vertices.shape[0]:
+        raise ValueError("closest_face: a face names a vertex outside [0, %d)" % vertices.shape[0])
+    if points.device.type == "cpu":
+        return closest_face_torch(points, triangle_table(vertices.to(points.dtype), faces))
+    from . import _mesh_ops
+    return _mesh_ops.closest_face(points.float().contiguous(), triangle_table(vertices.float(), faces), face_chunk)
 
 
 # ---- sampling -------------------------------------------------------------------------------------------------------------------
@@ -124,23 +228,41 @@ def _tkey(tau):
     return "%g" % tau
 
 
+def _surface_hits(points, vertices, faces):
+    """closest_face of the points on the mesh without its zero-area faces (float64 area, the faces sample_surface never draws
+    either) -> (d2 [Nq], unit normal of the hit face [Nq,3] float64)."""
+    v = vertices.double()
+    a, b, c = v[faces[:, 0]], v[faces[:, 1]], v[faces[:, 2]]
+    cross = torch.cross(b - a, c - a, dim=1)
+    twice = (cross[:, 0] * cross[:, 0] + cross[:, 1] * cross[:, 1] + cross[:, 2] * cross[:, 2]).sqrt()
+    keep = twice > 0
+    d2, hit = closest_face(points, vertices.float(), faces[keep])
+    return d2, cross[keep][hit] / twice[keep][hit].unsqueeze(1)
+
+
 @torch.no_grad()
-def mesh_distance(pred, gt, n_samples=100_000, seed=0, thresholds=(0.005, 0.01, 0.02), device="cuda:0", gt_transform=None):
+def mesh_distance(pred, gt, n_samples=100_000, seed=0, thresholds=(0.005, 0.01, 0.02), device="cuda:0", gt_transform=None, mode="samples"):
     """Metrics between the surfaces of pred and gt, each a (vertices [Nv,3], faces [Nf,3]) pair of arrays or tensors.  n_samples
     points are drawn on pred with `seed` and on gt with `seed + 1` (sample_surface), then `nearest` runs both ways on `device`.
     gt_transform: optional [4,4] (column-vector convention, x' = M[:3,:3] x + M[:3,3]) applied to the ground-truth vertices first.
+    mode: "samples" (default) measures every sample against the nearest SAMPLE of the other mesh; "surface" measures it against
+    the other SURFACE -- `closest_face`, the exact point-to-triangle distance minimised over the other mesh's faces (zero-area faces
+    dropped first) -- and takes the normal of the face that was hit.  The same samples, the same keys; no sampling floor.
 
     Conventions: distances are Euclidean, in the units of the meshes, NOT squared unless the name says so; nothing is halved.
-      accuracy            mean over the pred samples of the distance to the nearest gt sample
-      completeness        mean over the gt samples of the distance to the nearest pred sample
+      accuracy            mean over the pred samples of the distance to the nearest gt sample (mode "surface": to the gt surface)
+      completeness        mean over the gt samples of the distance to the nearest pred sample (mode "surface": to the pred surface)
       chamfer             accuracy + completeness
       chamfer_sq          the same sum with squared distances
       precision[tau]      share of the pred samples within tau of gt (<=);  recall[tau]: share of the gt samples within tau of pred
       fscore[tau]         2 P R / (P + R), 0 where P + R = 0
-      normal_consistency  mean |n . n'| of a sample's face normal and its nearest neighbour's, averaged over the two directions
+      normal_consistency  mean |n . n'| of a sample's face normal and its nearest neighbour's (mode "surface": the hit face's,
+                          float64), averaged over the two directions
       n_samples, pred_faces, gt_faces, pred_vertices, gt_vertices
     The per-threshold entries are dicts keyed by '%g' % tau.  Sample-to-sample distances carry the sampling floor: a surface against
-    itself measures about 0.5 sqrt(area / n_samples) per direction, not 0."""
+    itself measures about 0.5 sqrt(area / n_samples) per direction, not 0; sample-to-surface distances (mode "surface") measure 0."""
+    if mode not in ("samples", "surface"):
+        raise ValueError("mesh_distance: mode must be 'samples' or 'surface', not %r" % (mode,))
     dev = torch.device(device)
     pv, pf = _mesh_tensors(pred, dev)
     gv, gf = _mesh_tensors(gt, dev)
@@ -149,8 +271,13 @@ def mesh_distance(pred, gt, n_samples=100_000, seed=0, thresholds=(0.005, 0.01, 
         gv = (gv.double() @ m[:3, :3].T + m[:3, 3]).to(gv.dtype)
     pp, _, pn = sample_surface(pv, pf, n_samples, seed)
     gp, _, gn = sample_surface(gv, gf, n_samples, seed + 1)
-    d2_pg, i_pg = nearest(pp, gp)
-    d2_gp, i_gp = nearest(gp, pp)
+    if mode == "samples":
+        d2_pg, i_pg = nearest(pp, gp)
+        d2_gp, i_gp = nearest(gp, pp)
+        hit_p, hit_g = gn[i_pg].double(), pn[i_gp].double()
+    else:
+        d2_pg, hit_p = _surface_hits(pp, gv, gf)
+        d2_gp, hit_g = _surface_hits(gp, pv, pf)
     d_pg, d_gp = d2_pg.double().sqrt(), d2_gp.double().sqrt()
     out = {"accuracy": float(d_pg.mean()), "completeness": float(d_gp.mean())}
     out["chamfer"] = out["accuracy"] + out["completeness"]
@@ -160,8 +287,8 @@ def mesh_distance(pred, gt, n_samples=100_000, seed=0, thresholds=(0.005, 0.01, 
         p, r = float((d_pg <= tau).double().mean()), float((d_gp <= tau).double().mean())
         out["precision"][_tkey(tau)], out["recall"][_tkey(tau)] = p, r
         out["fscore"][_tkey(tau)] = 2 * p * r / (p + r) if p + r > 0 else 0.0
-    nc_p = (pn.double() * gn[i_pg].double()).sum(1).abs().mean()
-    nc_g = (gn.double() * pn[i_gp].double()).sum(1).abs().mean()
+    nc_p = (pn.double() * hit_p).sum(1).abs().mean()
+    nc_g = (gn.double() * hit_g).sum(1).abs().mean()
     out["normal_consistency"] = 0.5 * (float(nc_p) + float(nc_g))
     out.update(n_samples=int(n_samples), pred_faces=int(pf.shape[0]), gt_faces=int(gf.shape[0]), pred_vertices=int(pv.shape[0]),
                gt_vertices=int(gv.shape[0]))
@@ -196,11 +323,12 @@ def _flat(m):
     return out
 
 
-def evaluate_meshes(pred_dir, gt_dir, n_samples=100_000, seed=0, thresholds=(0.005, 0.01, 0.02), device="cuda:0", gt_transform=None, log=None):
+def evaluate_meshes(pred_dir, gt_dir, n_samples=100_000, seed=0, thresholds=(0.005, 0.01, 0.02), device="cuda:0", gt_transform=None, log=None,
+                    mode="samples"):
     """frame_<i>.ply of pred_dir against the i-th ground-truth mesh of gt_dir (its .obj / .ply files in natural sort order), for
     every i.  A different number of frames and ground-truth meshes is an error.  Writes <pred_dir>/mesh_metrics.json:
     {"frames": [{"frame": i, "pred": ..., "gt": ..., <metrics>}], "mean": {<metric>: mean over the frames}, "settings": ...} with
-    the per-threshold metrics flattened to 'fscore@0.01', and returns that dict."""
+    the per-threshold metrics flattened to 'fscore@0.01', and returns that dict.  mode: as in mesh_distance, recorded under "settings"."""
     frames = {}
     for name in os.listdir(pred_dir):
         m = re.fullmatch(r"frame_(\d+)\.ply", name)
@@ -215,7 +343,7 @@ def evaluate_meshes(pred_dir, gt_dir, n_samples=100_000, seed=0, thresholds=(0.0
     rows = []
     for i in range(len(gts)):
         m = _flat(mesh_distance(read_mesh(os.path.join(pred_dir, frames[i])), read_mesh(os.path.join(gt_dir, gts[i])), n_samples=n_samples,
-                                seed=seed, thresholds=thresholds, device=device, gt_transform=gt_transform))
+                                seed=seed, thresholds=thresholds, device=device, gt_transform=gt_transform, mode=mode))
         rows.append(dict({"frame": i, "pred": frames[i], "gt": gts[i]}, **m))
         if log is not None:
             log("frame %d (%s vs %s): chamfer %.6f, accuracy %.6f, completeness %.6f, normal consistency %.4f"
@@ -223,7 +351,7 @@ def evaluate_meshes(pred_dir, gt_dir, n_samples=100_000, seed=0, thresholds=(0.0
     keys = [k for k in rows[0] if k not in ("frame", "pred", "gt")]
     result = {"frames": rows, "mean": {k: sum(r[k] for r in rows) / len(rows) for k in keys},
               "settings": {"n_samples": int(n_samples), "seed": int(seed), "thresholds": [float(t) for t in thresholds], "device": str(device),
-                           "gt_transform": None if gt_transform is None else np.asarray(gt_transform, dtype=np.float64).tolist()}}
+                           "mode": mode, "gt_transform": None if gt_transform is None else np.asarray(gt_transform, dtype=np.float64).tolist()}}
     with open(os.path.join(pred_dir, "mesh_metrics.json"), "w") as fh:
         json.dump(result, fh, indent=1)
     return result
@@ -239,8 +367,11 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--thresholds", type=float, nargs="*", default=[0.005, 0.01, 0.02])
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--mode", choices=("samples", "surface"), default="samples",
+                    help="samples: sample to nearest sample (carries the sampling floor); surface: sample to the other surface, exact")
     a = ap.parse_args(argv)
-    return evaluate_meshes(a.pred_dir, a.gt_dir, n_samples=a.samples, seed=a.seed, thresholds=tuple(a.thresholds), device=a.device, log=print)
+    return evaluate_meshes(a.pred_dir, a.gt_dir, n_samples=a.samples, seed=a.seed, thresholds=tuple(a.thresholds), device=a.device, log=print,
+                           mode=a.mode)
 
 
 if __name__ == "__main__":

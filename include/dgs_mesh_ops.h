@@ -1,7 +1,7 @@
 /*
  * dgs_mesh_ops.h -- C ABI of the mesh kernels: depth-map fusion into a truncated signed distance volume, marching tetrahedra over
- * it, and the all-pairs nearest-neighbour search behind the geometry metrics of dgs_amd/mesh_metrics.py.  The first two replace
- * the PyTorch / open3d path of the reference's render_mesh.py:
+ * it, and the all-pairs nearest-neighbour and closest-triangle searches behind the geometry metrics of dgs_amd/mesh_metrics.py.
+ * The first two replace the PyTorch / open3d path of the reference's render_mesh.py:
  *
  *   dgs_tsdf_integrate          <-  utils/mesh_utils.py:218-266  compute_sdf_perframe + compute_unbounded_tsdf (inv_contraction=None)
  *   dgs_mt_classify / _emit     <-  utils/mesh_utils.py:158-199 / :268-271  volume.extract_triangle_mesh() / marching_cubes_with_contraction
@@ -94,6 +94,44 @@ int dgs_nn_search(long long n_query, const float* query, long long n_ref, const 
 
 /* out = {queries per workgroup, reference points per LDS round, default ref_chunk}: the sizes at which the kernel changes path. */
 int dgs_nn_layout(int out[3]);
+
+/* Closest triangle of every query point (brute force, all pairs): the exact point-to-triangle distance behind
+ * mesh_distance(mode="surface").  Version 2 libraries from this commit on also carry the dgs_tri_* pair; the version number is
+ * unchanged because nothing that existed before changes.  For every query P
+ *   best[P] = min over f in [0, n_tri) of ((unsigned long long)bits(d2(P, f)) << 32 | f)
+ * -- the packing and the meaning of dgs_nn_search: the smallest squared distance and, among equal ones, the lowest face index.
+ *
+ * THE TABLE.  One row of fp32 values per triangle, computed once outside the kernel (dgs_amd/mesh_metrics.py: triangle_table,
+ * elementwise PyTorch).  With corners A, B, C, dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z and
+ * cross(a, b) = (a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x), every operation rounded on its own:
+ *   e0 = B - A, e1 = C - B, e2 = A - C (edge k starts at O0 = A, O1 = B, O2 = C);   n = cross(e0, C - A);   m_k = cross(n, e_k)
+ *   r_k = 1 / dot(e_k, e_k) where dot(e_k, e_k) > 0 and the quotient is finite, else 0;   rn = 1 / dot(n, n) under the same rule
+ *   row = A, B, C, e0, e1, e2, n, m0, m1, m2 (three floats each), r0, r1, r2, rn, then two floats of padding (never read into the
+ *   arithmetic): 34 values in a row of 36 floats = 144 bytes, a multiple of 16.  dgs_tri_layout reports the row length.
+ *
+ * THE PAIR.  For a query P and a row, every operation a separately rounded fp32 one (-ffp-contract=off; dgs_amd/mesh_metrics.py:
+ * closest_face_torch states the same arithmetic in PyTorch):
+ *   for k in 0..2:  w_k = P - O_k;  t = min(max(dot(w_k, e_k) * r_k, 0), 1);  c = w_k - t * e_k;  s_k = dot(c, c)
+ *   best   = min(min(s_0, s_1), s_2)                                       the three edge segments
+ *   inside = dot(w_0, m_0) >= 0 && dot(w_1, m_1) >= 0 && dot(w_2, m_2) >= 0 && rn > 0
+ *   h = dot(w_0, n);  pl = (h * h) * rn                                     the plane, where P projects into the triangle
+ *   d2 = inside ? min(pl, best) : best
+ * No division and no branch per pair.  A triangle with collinear or coincident corners has rn = 0 and acts as its segments, a
+ * zero-length edge has r_k = 0 and acts as its origin: no NaN.  d2 >= 0, so its bit pattern orders like its value.  Coordinates
+ * are expected to be finite and of a size whose squares and fourth powers stay finite in fp32 (the Python wrapper refuses
+ * non-finite ones); a pair whose d2 is NaN never wins.
+ *   query [n_query,3] fp32;   table [n_tri,36] fp32, 16-byte aligned;   best [n_query] -- set to all-ones on `stream` by this call
+ *   tri_chunk: slices of tri_chunk triangles (the last one ragged), one grid row per slice, merged in `best` by one 64-bit atomic
+ *     minimum per query and slice, so the result does not depend on tri_chunk (values above n_tri mean one slice).
+ * Refused with a negative status before any launch: n_tri < 1, n_tri >= 2^31, n_query < 0, tri_chunk < 1, a null pointer with a
+ * non-zero count, a table that is not 16-byte aligned, more than 65535 slices.  n_query == 0 returns 0 and launches nothing.  A
+ * triangle of the last, ragged round or slice is never read past n_tri: tails are index guards, no padded triangle exists that
+ * could win. */
+int dgs_tri_search(long long n_query, const float* query, long long n_tri, const float* table, long long tri_chunk,
+                   unsigned long long* best, void* stream);
+
+/* out = {queries per workgroup, triangles per LDS round, default tri_chunk, floats per table row}. */
+int dgs_tri_layout(int out[4]);
 
 #ifdef __cplusplus
 }
