@@ -28,28 +28,12 @@ namespace dgs {
 #ifndef DGS_FWD_MINWAVES
 #define DGS_FWD_MINWAVES 5   // (the long-tile path's extra state must not cost the short path its fifth wave per SIMD)
 #endif
-#ifndef DGS_PIN_PREFETCH
-#define DGS_PIN_PREFETCH 1
-#endif
-// ---- A/B switches ------------------------------------------------------------------------------------------------------------
-// The product library is built with NONE of these set: the superseded kernels and reductions they select live in csrc/ab/ and are
-// only reachable with -DDGS_AB_BUILD (tools/ab_variants.sh builds such twins next to the product, tools/ab_check.sh runs the parity
-// file and the timing on each).  DGS_DIAG_BWD modes produce WRONG results by design (they remove work to price it).
-#ifndef DGS_FWD_ROWS
-#define DGS_FWD_ROWS 1       // 0: ab/blend_fwd_quadrant.h (one list per wave)
-#endif
-#ifndef DGS_BWD_ROWS
-#define DGS_BWD_ROWS 0       // 1: ab/blend_bwd_rows.h (one list per 16-lane row: 2.6 x slower on the L2's float-atomic rate)
-#endif
-#ifndef DGS_BWD_REDUCE
-#define DGS_BWD_REDUCE 4     // 0-3: ab/reduce_variants.h (3 = the DPP sum of wave_reduce.h), 4: transposition through the wave's own LDS (wave_reduce.h)
-#endif
-#ifndef DGS_DIAG_BWD
-#define DGS_DIAG_BWD 0       // 1 no atomics, 2 no reduction either, 3 evaluation + loop only
-#endif
-#if !defined(DGS_AB_BUILD) && (DGS_FWD_ROWS != 1 || DGS_BWD_ROWS != 0 || DGS_BWD_REDUCE != 4 || DGS_DIAG_BWD != 0)
-#error "A/B variants and diagnostic modes are not part of the product library: build them with -DDGS_AB_BUILD (tools/ab_variants.sh)"
-#endif
+// ---- tunables ----------------------------------------------------------------------------------------------------------------
+// What is left to the command line are values, not code paths: DGS_FWD_MINWAVES above, DGS_BWD_MINWAVES and DGS_BWD_CHUNK below,
+// each with its measurement where it is defined (tools/ab_variants.sh builds twins with other values next to the product,
+// tools/ab_check.sh runs the parity file and the timing on each).  The kernels and reductions that lost their measurement -- the
+// one-list-per-wave forward, the row-per-block backward, four earlier wave reductions -- are in the git history; what retired each
+// is the table of DESIGN.md section 4.
 constexpr int kChunk = 64;   // list entries staged per wave and step: one per lane
 
 __device__ __forceinline__ Quad as_quad(const float4& v) { return Quad{v.x, v.y, v.z, v.w}; }
@@ -381,17 +365,18 @@ __device__ __forceinline__ int lane_rank(unsigned long long m)
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
-#if !DGS_FWD_ROWS
-#include "ab/blend_fwd_quadrant.h"   // (DGS_AB_BUILD only, checked above)
-#endif
-
 // ---- forward blend, one list per 16-lane row (round 4) ----------------------------------------------------------------------
-// Same idea as ab/blend_bwd_rows.h, where it is described; in the forward nothing is summed across lanes and nothing is
-// added to global memory, so the design pays here: every DPP row of the wave -- one 4x4 pixel block of the quadrant -- walks the
-// list of the entries that can reach ITS block (blocks_hit_linear while staging; a block whose 16 pixels are all finished takes no
-// more entries), the planes of an entry are stored once per wave, and the visit loop runs max-over-rows(list length) times with
-// four slot addresses per LDS read instead of one.  Per-pixel arithmetic and entry order are those of the round-3 forward (ab/blend_fwd_quadrant.h): the results
-// are bit-identical.  0.87 of that kernel's visits on the 200k / 800x800 scene (tools/blend_stats.py).
+// Every DPP row of the wave -- one 4x4 pixel block of the quadrant (surfel_math.h lane_pixel) -- walks the list of the entries that can
+// reach ITS block: while staging, a lane tests its entry against the four blocks (blocks_hit_linear: the record's pixel box, then a
+// tangent-plane bound of the footprint's conic; also what decides whether the entry is staged at all; a block whose 16 pixels are all
+// finished takes no more entries), the entry's planes are stored once per wave, compacted, and each block it reaches gets the slot
+// number appended to its row's byte list (rank among the ballot of that block).  One wave-instruction of the visit loop then serves
+// four (entry, block) pairs: lane l reads the planes of the slot its row is at (four addresses per ds_read_b128), rows that have run
+// out of entries read the null slot (opacity 0: fails the alpha test), and the loop runs max-over-rows(list length) times.  In the
+// forward nothing is summed across lanes and nothing is added to global memory, so the design pays here (the same design lost in the
+// backward: DESIGN.md section 4).  Per-pixel arithmetic and entry order are those of the one-list-per-wave forward of round 3 that it
+// replaced (0.126 -> 0.120 ms): the results are bit-identical.  0.87 of that kernel's visits on the 200k / 800x800 scene
+// (tools/blend_stats.py).
 
 // ---- long tiles (round 4) ---------------------------------------------------------------------------------------------------
 // A tile is one workgroup and a quadrant one wave that walks the tile's list serially, so a launch is never shorter than its longest
@@ -488,7 +473,7 @@ __device__ __forceinline__ void blend_fwd_long(const BlendFwdArgs& a, int tile, 
         const uint32_t e_mine = base + 64u * (uint32_t)seg + (uint32_t)lane;
         const uint32_t id = id_next;
         id_next = e_mine + 4 * kChunk < len ? a.point_list[range.x + e_mine + 4 * kChunk] : 0u;
-        // stage the wave's chunk (as blend_fwd_kernel: the entries that can touch the quadrant, compacted)
+        // stage the wave's chunk (one list for the whole quadrant here: the entries that can touch it, compacted)
         const float4* src = a.rec + (size_t)id * kRecQuads;
         const float4 q0 = src[0], q1 = src[1], q2 = src[2], q3r = src[3], q4r = src[4], bx = src[5];
         const TileAffine ta = tile_affine(as_quad(q0), as_quad(q1), as_quad(q2), X0, Y0);
@@ -687,6 +672,11 @@ __global__ void __launch_bounds__(kTilePix, DGS_FWD_MINWAVES) blend_fwd_rows_ker
     PixFwd st;
     pixfwd_init(st);
 
+    // Visit, in list order, the entries the wave has staged.  Every instruction of this loop is issued once per visit, scalar ones
+    // included (the CU's scalar unit issues ~1 instruction per cycle for all four SIMDs: 25 scalar instructions per visit -- bit-scan
+    // of a visit mask, saturation ballots, early-out tests -- cost as much issue time as the arithmetic).  Hence: the staged entries
+    // are COMPACTED (a counted loop), a pixel that saturates (forward.cu:402-406: it blends neither this entry nor any later one) is
+    // poisoned with one select, and whether the wave still has live pixels is tested per chunk, not per visit.
     auto visit = [&](auto track_median, int niter) {
         int sl = my_list[0];
         int sl_next = my_list[1];
@@ -695,9 +685,11 @@ __global__ void __launch_bounds__(kTilePix, DGS_FWD_MINWAVES) blend_fwd_rows_ker
         for (int i = 0; i < niter; i++) {
             AlphaEval e;
             const bool pass = alpha_affine(us, vs, as_quad(a0), as_quad(a1), as_quad(a2), e);
-#if DGS_PIN_PREFETCH
-            asm volatile("" : "+v"(e.a), "+v"(e.alpha) : : "memory");   // see blend_fwd_rows_kernel: one register set, loads pinned behind their last use
-#endif
+            // Software pipeline over the visited entries with ONE register set: the next entry's alpha part is requested as soon
+            // as this one's has been consumed, its Tw / normal / colour at the end of the visit -- each INTO THE SAME registers,
+            // a good hundred cycles before it is needed.  The empty asm statements pin the order: left alone the compiler hoists
+            // the loads above the evaluation, needs a second register set and pays twelve moves per visit to rotate it.
+            asm volatile("" : "+v"(e.a), "+v"(e.alpha) : : "memory");
             sl = sl_next;
             a0 = S.a[0][sl]; a1 = S.a[1][sl]; a2 = S.a[2][sl];
             bool use3d;
@@ -711,9 +703,7 @@ __global__ void __launch_bounds__(kTilePix, DGS_FWD_MINWAVES) blend_fwd_rows_ker
                 pixfwd_accumulate<decltype(track_median)::value>(st, w, test_T, depth, as_quad(q3), Quad{q4.x, q4.y, 0.f, 0.f});
             }
             us = (ok ^ blend) ? __builtin_nanf("") : us;   // passed but saturated: the pixel is finished
-#if DGS_PIN_PREFETCH
             asm volatile("" : "+v"(st.T), "+v"(us) : : "memory");
-#endif
             tw = S.tw[sl]; q3 = S.q3[sl]; q4 = S.q4[sl];
             sl_next = my_list[i + 2];
             asm volatile("" : "+v"(sl_next));   // requested here, a visit before the address is formed from it
@@ -725,8 +715,12 @@ __global__ void __launch_bounds__(kTilePix, DGS_FWD_MINWAVES) blend_fwd_rows_ker
     for (uint32_t base = 0; base < len && alive != 0ull; base += kChunkF) {
         const uint32_t e_mine = base + (uint32_t)lane;
         const uint32_t id = id_next;   // (lanes beyond the end of the list hold id 0: a valid record, masked out below)
+        // Straight-line staging: all six quads of the record are requested at once and every lane runs the whole test (a
+        // conditional ladder -- list end, box, footprint -- makes the compiler sink each load behind the test before it:
+        // five dependent trips to memory per chunk).  Entries that can touch the quadrant are compacted: slot = rank among them.
         const float4* src = a.rec + (size_t)id * kRecQuads;
         const float4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3], q4 = src[4], bx = src[5];
+        // the id of the lane's next entry travels while this chunk is visited (the record loads of the next step then start at once)
         id_next = e_mine + kChunkF < len ? a.point_list[range.x + e_mine + kChunkF] : 0u;
         const TileAffine ta = tile_affine(as_quad(q0), as_quad(q1), as_quad(q2), X0, Y0);
         uint32_t bm = e_mine < len ? blocks_hit_linear(ta, qus0, qvs0, as_quad(bx), qx, qy) : 0u;
@@ -763,6 +757,8 @@ __global__ void __launch_bounds__(kTilePix, DGS_FWD_MINWAVES) blend_fwd_rows_ker
         alive = ballot64(us == us);   // wave-level early out (forward.cu:334-336 votes per block)
     }
 
+    // per-tile maximum of the last contributor: the backward starts there instead of walking the
+    // whole list (backward.cu:276-279 skips those entries one by one)
     uint32_t mx = inside ? st.last : 0u;
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
@@ -825,41 +821,16 @@ struct BlendBwdArgs {
 // ---- wave reduction of the 16 per-surfel partials of one (wave, entry) visit --------------------------------------------
 // Transposition through the wave's own LDS (wave_reduce.h: 16 ds_write_addtid_b32 + 4 ds_read_b128 + 17 VALU), in two rounds of
 // 8 values through 2 KB per wave.  The four earlier implementations (butterfly on the LDS crossbar 0.338 ms, matrix pipe 0.548,
-// permlane + MFMA hybrid 0.455, permlane + DPP 0.304-0.315; this one 0.267) and their measurements: ab/reduce_variants.h.
+// permlane + MFMA hybrid 0.455, permlane + DPP 0.304-0.315; this one 0.267; one round of 16 values through 4 KB -- 3 workgroups
+// per CU instead of 5 -- 0.304) and their measurements: DESIGN.md section 4.
 // On return lane l with (l & 3) == 0 holds the wave total of v[(l >> 3) + 2 (l & 4)]; reduce16_slot() says so.
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-#ifndef DGS_RED_PHASES
-#define DGS_RED_PHASES 2     // 1 (A/B): one round of 16 values through 4 KB -- 3 workgroups per CU instead of 5: 0.304 ms
-#endif
-#if !defined(DGS_AB_BUILD) && DGS_RED_PHASES != 2
-#error "DGS_RED_PHASES is an A/B switch: -DDGS_AB_BUILD"
-#endif
+struct BwdRed { float v[8][64]; };   // one wave's transposition buffer
+typedef RedLds BwdRedCtx;
 
-#if DGS_BWD_REDUCE != 4
-#include "ab/reduce_variants.h"   // defines BwdRedCtx, wave_reduce16, reduce16_slot for variants 0-3
-#else
-struct BwdRed { float v[16 / DGS_RED_PHASES][64]; };   // one wave's transposition buffer
-typedef RedLds<DGS_RED_PHASES> BwdRedCtx;
-
-__device__ __forceinline__ float wave_reduce16(float (&v)[16], int lane, const BwdRedCtx& rc)
-{
-#if DGS_RED_PHASES == 1
-    return wave_reduce16_lds(v, rc);
-#else
-    return wave_reduce16_lds(v, rc, lane);
-#endif
-}
+__device__ __forceinline__ float wave_reduce16(float (&v)[16], int lane, const BwdRedCtx& rc) { return wave_reduce16_lds(v, rc, lane); }
 
 // which of the 16 values lane `lane` holds after wave_reduce16, or -1 if the lane holds a duplicate
-__device__ __forceinline__ int reduce16_slot(int lane)
-{
-#if DGS_RED_PHASES == 2
-    return (lane & 3) == 0 ? (lane >> 3) + 2 * (lane & 4) : -1;
-#else
-    return (lane & 3) == 0 ? (lane >> 2) : -1;
-#endif
-}
-#endif
+__device__ __forceinline__ int reduce16_slot(int lane) { return (lane & 3) == 0 ? (lane >> 3) + 2 * (lane & 4) : -1; }
 
 __device__ __forceinline__ float wave_sum(float v)
 {
@@ -868,7 +839,7 @@ __device__ __forceinline__ float wave_sum(float v)
     return v;
 }
 
-constexpr int kDetRows = DGS_BWD_ROWS ? 16 : 4;   // rows of det_part per list entry: one per (wave, 16-lane row) or per wave
+constexpr int kDetRows = 4;   // rows of det_part per list entry: one per wave
 
 #ifndef DGS_BWD_MINWAVES
 #define DGS_BWD_MINWAVES 5
@@ -888,9 +859,8 @@ __device__ __forceinline__ unsigned long long to_fixed44(float v)
     return (unsigned long long)__float2ll_rn(v * 17592186044416.0f);   // 2^44; two's complement: unsigned wrap-around adds signed numbers
 }
 
-#ifdef DGS_COUNT_VISITS   // development build (tools/diag/visit_counts.py): what the backward's visits are made of
-__device__ unsigned long long g_visit_counts[4];   // visits of the real pass | of them with no blending lane | blending lanes of the others | staged entries
-#endif
+// 48 entries per chunk and DGS_BWD_MINWAVES 5 go together: 30 KB of LDS = 5 workgroups per CU, 0.267 ms at 200k / 800x800; 64 entries
+// at 4 workgroups per CU: 0.281 -- the occupancy decides, the chunk size does not
 #ifndef DGS_BWD_CHUNK
 #define DGS_BWD_CHUNK 48
 #endif
@@ -973,9 +943,6 @@ __device__ __forceinline__ void bwd_quadrant(const BlendBwdArgs& a, int tile, in
 
     // chunk lane l holds list entry e = top - l; the entries that can touch the quadrant are compacted in that (back to front) order
     const bool stager = kChunkB == 64 || lane < kChunkB;
-#ifdef DGS_COUNT_VISITS
-    unsigned long long n_visit = 0, n_empty = 0, n_lanes = 0, n_staged = 0;
-#endif
     auto walk = [&](auto light_tag) {
         constexpr bool kLight = decltype(light_tag)::value;
         uint32_t id_next = stager && hi - 1 - lane >= lo ? a.point_list[range.x + (uint32_t)(hi - 1 - lane)] : 0u;
@@ -1002,31 +969,20 @@ __device__ __forceinline__ void bwd_quadrant(const BlendBwdArgs& a, int tile, in
             }
             __builtin_amdgcn_wave_barrier();   // the slice is private to this wave: its LDS writes above are ordered before its reads below
             const int nhit = __builtin_popcountll(m);
-#ifdef DGS_COUNT_VISITS
-            if (!kLight) n_staged += (unsigned long long)__builtin_popcountll(ballot64(stager & (e_mine >= lo)));
-#endif
             f32x4 a0 = S.a[0][0], a1 = S.a[1][0], a2 = S.a[2][0];
             f32x4 tw = S.tw[0], tuv = S.tuv[0], q3 = S.q3[0], q4 = S.q4[0];
             for (int i = 0; i < nhit; i++) {
                 AlphaEval ev;
                 bool ok = alpha_affine(us, vs, as_quad(a0), as_quad(a1), as_quad(a2), ev);
-#if DGS_PIN_PREFETCH
                 asm volatile("" : "+v"(ev.a), "+v"(ev.alpha) : : "memory");   // see blend_fwd_rows_kernel: one register set, loads pinned behind their last use
-#endif
                 a0 = S.a[0][i + 1]; a1 = S.a[1][i + 1]; a2 = S.a[2][i + 1];
                 DGS_PIN4(a0); DGS_PIN4(a1); DGS_PIN4(a2);
                 const int e = __builtin_amdgcn_readfirstlane(__float_as_int(q4.z));  // 0-based list index == the reference's `contributor`
                 ok = ok & (e < st.last_contributor);
-#ifdef DGS_COUNT_VISITS
-                if (!kLight) { n_visit++; if (ballot64(ok) == 0ull) n_empty++; }
-#endif
                 if (ballot64(ok) != 0ull) {
                     bool use3d;
                     const float depth = alpha_depth(ev, tw.x, tw.y, tw.z, use3d);
                     ok = ok & (depth >= kNear);
-#ifdef DGS_COUNT_VISITS
-                    if (!kLight) n_lanes += (unsigned long long)__builtin_popcountll(ballot64(ok));
-#endif
                     if (kLight) {
                         // pass 1 of a long tile: only what the two recurrences need (pixbwd_step_affine's alpha, 1 / (1 - alpha) and u)
                         const float alpha = ok ? ev.alpha : 0.f;
@@ -1037,14 +993,8 @@ __device__ __forceinline__ void bwd_quadrant(const BlendBwdArgs& a, int tile, in
                     } else {
                     // every lane runs the step; a lane that does not blend the entry contributes exact zeros (pixbwd_step_affine)
                     float out[16], out2d[2];
-#if DGS_DIAG_BWD == 3
-                    for (int k = 0; k < 16; k++) out[k] = depth;
-                    out2d[0] = out2d[1] = 0.f;
-                    asm volatile("" : : "v"(depth), "v"(tuv.x), "v"(q3.x), "v"(q4.x));
-#else
                     pixbwd_step_affine(st, ev, ok, use3d, depth, e, pfx, pfy, tw.x, tw.y, as_quad(tuv), tw.w, as_quad(q3),
                                        Quad{q4.x, q4.y, 0.f, 0.f}, out, out2d);
-#endif
                     // (two ballots of plain comparisons and scalar logic: ballot64(ok && !use3d) compiled to a select and a compare per visit)
                     const bool any2d = (ballot64(ok) & ~ballot64(use3d)) != 0ull;
                     // wave-uniform row address: keep it on the scalar unit (SGPR base + per-lane offset in the atomic)
@@ -1052,22 +1002,12 @@ __device__ __forceinline__ void bwd_quadrant(const BlendBwdArgs& a, int tile, in
                                                 : (size_t)__builtin_amdgcn_readfirstlane(__float_as_uint(q4.w)) * kAccFloats;
                     float* dst = (DET == 1 ? a.det_part : a.acc) + row;
                     unsigned long long* dst64 = DET == 2 ? a.acc64 + row : nullptr;
-#if DGS_DIAG_BWD >= 2
-                    float tot = 0.f;
-                    for (int k = 0; k < 16; k++) asm volatile("" : : "v"(out[k]));
-                    asm volatile("" : : "s"(dst));
-#else
                     const float tot = wave_reduce16(out, lane, rc);
-#endif
-#if DGS_DIAG_BWD == 0
                     if (rslot >= 0) {
                         if (DET == 1) dst[rslot] = tot;
                         else if (DET == 2) atomicAdd(dst64 + rslot, to_fixed44(tot));
                         else atomicAdd(dst + rslot, tot);
                     }
-#else
-                    asm volatile("" : : "v"(tot));
-#endif
                     if (any2d) {  // rare 2-D filter branch (backward.cu:436-443)
                         const float mx = wave_sum(out2d[0]);
                         const float my = wave_sum(out2d[1]);
@@ -1079,9 +1019,7 @@ __device__ __forceinline__ void bwd_quadrant(const BlendBwdArgs& a, int tile, in
                     }
                     }
                 }
-#if DGS_PIN_PREFETCH
                 asm volatile("" : "+v"(st.T) : : "memory");
-#endif
                 tw = S.tw[i + 1]; tuv = S.tuv[i + 1]; q3 = S.q3[i + 1]; q4 = S.q4[i + 1];
                 DGS_PIN4(tw); DGS_PIN4(tuv); DGS_PIN4(q3); DGS_PIN4(q4);
             }
@@ -1106,33 +1044,22 @@ __device__ __forceinline__ void bwd_quadrant(const BlendBwdArgs& a, int tile, in
         __syncthreads();   // xfer lives in the reduction buffers, which the real pass writes
     }
     walk(std::false_type{});
-#ifdef DGS_COUNT_VISITS
-    if (lane == 0) {
-        atomicAdd(&g_visit_counts[0], n_visit); atomicAdd(&g_visit_counts[1], n_empty);
-        atomicAdd(&g_visit_counts[2], n_lanes); atomicAdd(&g_visit_counts[3], n_staged);
-    }
-#endif
 }
 
 template <int DET>
 __global__ void __launch_bounds__(kTilePix, DGS_BWD_MINWAVES) blend_bwd_kernel(BlendBwdArgs a)  // workgroups per CU = waves per SIMD the register allocator must allow
 {
     __shared__ BwdStage s_stage[4];
-#if DGS_BWD_REDUCE == 4
     __shared__ BwdRed s_red[4];
     static_assert(sizeof(BwdRed) * 4 >= 4 * 3 * 64 * sizeof(float), "the long path's transfer table lives in the reduction buffers");
-#endif
 
     const int ntiles = a.tiles_x * a.tiles_y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (a.clean_flag && blockIdx.x == 0 && threadIdx.x == 0) *a.clean_flag = 0u;   // (prep_bwd_kernel read it in the launch before)
     int tile, lq = -1;
-#if DGS_BWD_REDUCE == 4
     if (a.long_thr) {   // tile order 3 with the long-tile path (long_decode)
         if (!long_decode(blockIdx.x, a.order, ntiles, a.long_thr->bwd, a.tile_last, a.ranges, tile, lq)) return;
-    } else
-#endif
-    {
+    } else {
         tile = tile_for_block(blockIdx.x, a.tiles_x, a.tiles_y, a.mode);
         if (a.mode < 3 && tile >= ntiles) return;
         if (a.mode >= 3) tile = (int)a.order[tile];
@@ -1140,19 +1067,13 @@ __global__ void __launch_bounds__(kTilePix, DGS_BWD_MINWAVES) blend_bwd_kernel(B
     }
     if (a.tile_last[tile] == 0u) return;   // no pixel of the tile blended anything
     BwdRedCtx rc;
-#if DGS_BWD_REDUCE == 4
     rc.init(&s_red[wave].v[0][0], lane);
     if (lq >= 0) {
         bwd_quadrant<DET, true>(a, tile, lq, wave, s_stage[wave], rc, &s_red[0].v[0][0]);
         return;
     }
-#endif
     bwd_quadrant<DET, false>(a, tile, wave, 0, s_stage[wave], rc, nullptr);
 }
-
-#if DGS_BWD_ROWS
-#include "ab/blend_bwd_rows.h"
-#endif
 
 // Deterministic variant 2: the fixed-point rows -> the float accumulator rows the per-surfel kernel reads; the fixed-point rows are
 // left zeroed for the next backward.

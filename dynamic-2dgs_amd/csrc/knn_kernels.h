@@ -437,9 +437,6 @@ int launch_knn_refine_q(int N, int M, int D, const float* x, const float* nodes,
 //     (distance, then index).  Two lanes (l, l + 32) share a point and own alternating groups of 4 rows of every 32-node tile (the
 //     D layout of the instruction); their top-K lists are merged at the end.  A garbage seed (T = inf) sets every bit: that lane
 //     scans its rows itself.
-#ifndef DGS_KNN_DIAG
-#define DGS_KNN_DIAG 0   // development only: 1 no candidate evaluation, 2 no MFMA loop, 8 report the candidate count
-#endif
 constexpr int kRmThreads = 512;   // 8 waves x 32 points
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -564,7 +561,7 @@ __global__ void __launch_bounds__(kRmThreads) knn_refine_mfma_kernel(int N, int 
 #pragma unroll
         for (int u = 0; u < 2; u++) {
             const int t = 2 * w + u;
-            if (t < ntiles && !(DGS_KNN_DIAG & 2)) {                     // wave-uniform
+            if (t < ntiles) {                                            // wave-uniform
                 const bf16x8 nh = __builtin_bit_cast(bf16x8, ahi[t * 64]), nl = __builtin_bit_cast(bf16x8, alo[t * 64]);
                 f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(nh, bh, cthr, 0, 0, 0);     // nh.xh + |n|^2 - thr
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(nl, bh, acc, 0, 0, 0);             // nl.xh   (|n|^2 slots of nl are 0)
@@ -597,10 +594,6 @@ __global__ void __launch_bounds__(kRmThreads) knn_refine_mfma_kernel(int N, int 
             }
         }
     };
-#if DGS_KNN_DIAG & 1
-#pragma unroll
-    for (int w = 0; w < TP; w++) bi[w % K] ^= (int)hits[w];      // (keeps the hit words alive)
-#else
     // every trip each lane takes ITS next candidate, whichever word it is in: the number of trips is the largest candidate count of a
     // lane (5-6), not the sum over the words of the largest count per word (14 with 1.6 candidates per lane spread over 8 words)
     for (;;) {
@@ -619,7 +612,6 @@ __global__ void __launch_bounds__(kRmThreads) knn_refine_mfma_kernel(int N, int 
             if (j < M) offer(full_dist(j), j);
         }
     }
-#endif
     // merge with the partner lane's list
     float od[K];
     int oi[K];

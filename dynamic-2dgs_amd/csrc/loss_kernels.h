@@ -99,9 +99,6 @@ __global__ void __launch_bounds__(256) loss_combine_kernel(CombineArgs c)
 // Every thread filters several adjacent outputs from one run of inputs held in registers (7 + 10 rows, 6 + 10 columns).  The
 // window weights are copied into VGPRs: a VALU instruction with an SGPR source issues at 4.4 instead of 2.5 cycles on gfx950
 // (profiles/r03_valu_issue_gfx950.txt).  LDS 36 KB forward / 22 KB backward.
-#ifndef DGS_SSIM_DIAG
-#define DGS_SSIM_DIAG 0   // development only: 1 no map stores, 2 no global loads, 4 no SSIM formula (tools/diag/loss_timing.py)
-#endif
 __device__ __forceinline__ void gauss_to_vgprs(const Gauss& g, float (&w)[11])
 {
 #pragma unroll
@@ -143,11 +140,7 @@ __device__ __forceinline__ void ssim_fwd_body(const SsimFwdArgs& A, const Gauss&
             const int y = y0 + rg * kPV + j - kR;
             const unsigned o = (unsigned)min(max(y, 0), H - 1) * (unsigned)W + xc;
             const bool in = xin && y >= 0 && y < H;
-#if DGS_SSIM_DIAG & 2
-            const float av = (float)(o & 255) * 0.003f, bv = (float)(o & 127) * 0.005f;
-#else
             const float av = p1[o], bv = p2[o];
-#endif
             a[j] = in ? av : 0.f;
             b[j] = in ? bv : 0.f;
         }
@@ -206,10 +199,6 @@ __device__ __forceinline__ void ssim_fwd_body(const SsimFwdArgs& A, const Gauss&
         for (int o = 0; o < kPH; o++) {
             const int x = x0 + c0 + o;
             const float mu1 = res[0][o], mu2 = res[1][o], s11 = res[2][o], s22 = res[3][o], s12 = res[4][o];
-#if DGS_SSIM_DIAG & 4
-            val += mu1 + mu2 + s11 + s22 + s12;
-            continue;
-#endif
             const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
             const float sg1 = s11 - mu1_sq, sg2 = s22 - mu2_sq, sg12 = s12 - mu12;
             const float A = 2.f * mu12 + kC1, B = 2.f * sg12 + kC2, Cc = mu1_sq + mu2_sq + kC1, D = sg1 + sg2 + kC2;
@@ -222,7 +211,7 @@ __device__ __forceinline__ void ssim_fwd_body(const SsimFwdArgs& A, const Gauss&
             res[2][o] = 2.f * A * inv_cd;
         }
     }
-    if (dm_dmu1 && !(DGS_SSIM_DIAG & 1)) {
+    if (dm_dmu1) {
         // The derivative maps leave through LDS: a thread's 6 adjacent outputs would be 4-byte stores 24 bytes apart (18 partial
         // cache lines per wave store; the three maps cost 12 of the kernel's 25 us that way), rows of 54 floats are 2-3 lines.
         __syncthreads();                       // every thread is done reading s_v

@@ -518,19 +518,6 @@ void dgs_profile_enable(int mode) { (void)dgs_context_profile_enable(default_con
 void dgs_profile_reset(void) { dgs_context_profile_reset(default_context()); }
 int dgs_profile_read(double* out, int cap) { return dgs_context_profile_read(default_context(), out, cap); }
 
-#ifdef DGS_COUNT_VISITS
-// development build only (-DDGS_COUNT_VISITS, tools/diag/visit_counts.py): the backward blend's visit counters, optionally cleared
-int dgs_debug_visit_counts(unsigned long long* out4, int reset)
-{
-    if (out4 && hipMemcpyFromSymbol(out4, HIP_SYMBOL(dgs::g_visit_counts), 4 * sizeof(unsigned long long)) != hipSuccess) return -1;
-    if (reset) {
-        const unsigned long long z[4] = {0, 0, 0, 0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(dgs::g_visit_counts), z, sizeof(z)) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#endif
-
 int dgs_debug_layout(int which, int P, int width, int height, int R, size_t* offsets, int cap)
 {
     std::vector<size_t> v;
@@ -790,12 +777,10 @@ int dgs_context_forward(dgs_context* ctx, dgs_alloc_fn geometry_alloc, void* geo
     fa.out_others = out_others;
     int grid = dgs::blend_grid_size(il.tiles_x, il.tiles_y, fa.mode);
     fa.long_thr = nullptr;
-#if DGS_FWD_ROWS
     if (fa.mode == 3 && ctx->long_tiles.load() && !ctx->grid_limit_fwd.load()) {   // long-tile path (kernels_blend.h): four workgroups for the longest lists
         fa.long_thr = (const dgs::LongThr*)(img + il.long_thr);
         grid = dgs::long_grid_size(il.ntiles);
     }
-#endif
     if (const int lim = ctx->grid_limit_fwd.load()) {
         grid = lim < grid ? lim : grid;
         DGS_HIP(hipMemsetAsync(img + il.final_T, 0, il.ranges - il.final_T, stream));   // final_T, n_contrib of the skipped tiles
@@ -816,11 +801,7 @@ int dgs_context_forward(dgs_context* ctx, dgs_alloc_fn geometry_alloc, void* geo
     }
     Prof::Pair pp;
     const bool timed = prof_begin(ctx, 0, stream, pp);
-#if DGS_FWD_ROWS
     hipLaunchKernelGGL(dgs::blend_fwd_rows_kernel, dim3(grid), dim3(dgs::kTilePix), 0, stream, fa);
-#else
-    hipLaunchKernelGGL(dgs::blend_fwd_kernel, dim3(grid), dim3(dgs::kTilePix), 0, stream, fa);
-#endif
     if (timed) prof_end(ctx, stream, pp, fa.tile_last, il.ntiles);
     DGS_STAGE("blend_fwd", debug, stream);
     return R;
@@ -868,7 +849,7 @@ int dgs_context_backward(dgs_context* ctx, int P, int D, int M, int R, const flo
         hipLaunchKernelGGL(dgs::prep_bwd_kernel, dim3(fill_blocks + 1), dim3(1024), 0, stream, (float4*)acc, n4,
                            (const uint32_t*)(img_buffer + il.tile_last), il.tiles_x, il.tiles_y, bwd_mode,
                            (uint32_t*)(img_buffer + il.order_bwd), (uint32_t*)(img_buffer + il.group_xcd), (uint32_t*)(img_buffer + il.long_thr), (uint32_t)ctx->long_div_bwd.load(),
-                           DGS_BWD_ROWS ? (const uint32_t*)nullptr : (const uint32_t*)(geom_buffer + gl.total) + 3);   // (the A/B rows kernel does not reset the flag)
+                           (const uint32_t*)(geom_buffer + gl.total) + 3);   // (the forward rider's flag; blend_bwd_kernel resets it)
         DGS_STAGE("prep_bwd", debug, stream);
     } else {
         DGS_HIP(hipMemsetAsync(acc, 0, acc_bytes, stream));
@@ -899,12 +880,10 @@ int dgs_context_backward(dgs_context* ctx, int P, int D, int M, int R, const flo
         ba.clean_flag = (uint32_t*)(geom_buffer + gl.total) + 3;
         int grid = dgs::blend_grid_size(il.tiles_x, il.tiles_y, ba.mode);
         ba.long_thr = nullptr;
-#if !DGS_BWD_ROWS && DGS_BWD_REDUCE == 4
         if (ba.mode == 3 && prep_fused && ctx->long_tiles.load() && !ctx->grid_limit_bwd.load()) {   // long-tile path (kernels_blend.h)
             ba.long_thr = (const dgs::LongThr*)(img_buffer + il.long_thr);
             grid = dgs::long_grid_size(il.ntiles);
         }
-#endif
         if (const int lim = ctx->grid_limit_bwd.load()) grid = lim < grid ? lim : grid;
         Prof::Pair pp;
         const bool timed = prof_begin(ctx, 1, stream, pp);
@@ -945,22 +924,14 @@ int dgs_context_backward(dgs_context* ctx, int P, int D, int M, int R, const flo
             DGS_HIP(hipMallocAsync((void**)&part, bytes, stream));
             DGS_HIP(hipMemsetAsync(part, 0, bytes, stream));
             ba.det_part = part;
-#if DGS_BWD_ROWS
-            hipLaunchKernelGGL(dgs::blend_bwd_rows_kernel<true>, dim3(grid), dim3(dgs::kTilePix), 0, stream, ba);
-#else
             hipLaunchKernelGGL(dgs::blend_bwd_kernel<1>, dim3(grid), dim3(dgs::kTilePix), 0, stream, ba);
-#endif
             hipLaunchKernelGGL(dgs::det_reduce_kernel, dim3((P + 255) / 256), dim3(256), 0, stream, P, radii,
                                (const uint2*)(geom_buffer + gl.rects), il.tiles_x, ba.ranges, ba.point_list, (const float*)part, acc);
             DGS_HIP(hipFreeAsync(part, stream));
         } else {
             ba.det_part = nullptr;
             ba.acc64 = nullptr;
-#if DGS_BWD_ROWS
-            hipLaunchKernelGGL(dgs::blend_bwd_rows_kernel<false>, dim3(grid), dim3(dgs::kTilePix), 0, stream, ba);
-#else
             hipLaunchKernelGGL(dgs::blend_bwd_kernel<0>, dim3(grid), dim3(dgs::kTilePix), 0, stream, ba);
-#endif
         }
         if (timed) prof_end(ctx, stream, pp, ba.tile_last, il.ntiles);
         DGS_STAGE("blend_bwd", debug, stream);

@@ -51,11 +51,21 @@ def _ops_module():
     return _ops
 
 
-def test_train_ops_deps_are_the_include_closure():
-    """_ops._deps() (what the stale-binary hash covers) is exactly the set of files train_ops.hip reaches through relative
-    #include "..." lines: a header missing from the list would hide kernel edits from the hash, a listed header that is no
-    longer included fails too."""
-    todo, seen = [os.path.join(CSRC, "train_ops.hip")], set()
+def _binding_module(name):
+    import importlib
+    _ops_module()   # (puts the package directory on sys.path)
+    return importlib.import_module(name)
+
+
+@pytest.mark.parametrize("module,source,header", [("dgs_amd._ops", "train_ops.hip", "dgs_train_ops.h"),
+                                                  ("diff_surfel_rasterization._C", "surfel_rasterizer.hip", "dgs_surfel_rasterizer.h"),
+                                                  ("dgs_amd._mesh_ops", "mesh_ops.hip", "dgs_mesh_ops.h")],
+                         ids=["train_ops", "rasterizer", "mesh_ops"])
+def test_library_deps_are_the_include_closure(module, source, header):
+    """A binding module's _deps() (what the stale-binary hash covers) is exactly the set of files its .hip file reaches through
+    relative #include "..." lines, plus its public header: a header missing from the list would hide kernel edits from the hash,
+    a listed header that is no longer included fails too."""
+    todo, seen = [os.path.join(CSRC, source)], set()
     while todo:
         path = os.path.normpath(todo.pop())
         if path in seen:
@@ -63,9 +73,10 @@ def test_train_ops_deps_are_the_include_closure():
         seen.add(path)
         for inc in re.findall(r'^\s*#\s*include\s*"([^"]+)"', open(path).read(), flags=re.M):
             todo.append(os.path.join(os.path.dirname(path), inc))
-    deps = [os.path.normpath(p) for p in _ops_module()._deps()]
+    want = seen | {os.path.join(ROOT, "include", header)}
+    deps = [os.path.normpath(p) for p in _binding_module(module)._deps()]
     assert len(deps) == len(set(deps))
-    assert set(deps) == seen, (sorted(set(deps) - seen), sorted(seen - set(deps)))
+    assert set(deps) == want, (sorted(set(deps) - want), sorted(want - set(deps)))
 
 
 def _prototypes(header):

@@ -1,5 +1,5 @@
 #!/bin/bash
-# On the GPU box: bench.py headline (no legs) under several environment settings, interleaved, N rounds; then one kernel timeline.
+# On the GPU box: bench.py headline (value and ms/step, no legs) under any number of environment settings, interleaved, N rounds.
 #   tools/ab_env.sh ROUNDS "NAME=VALUE ..." "NAME=VALUE ..." ...
 R=$(cd "$(dirname "$0")/.." && pwd)
 N=$1; shift

@@ -1,7 +1,9 @@
 #!/bin/bash
-# A/B builds of the rasterizer library with extra -D flags, timed back to back on ONE lease (tools/quick_timing.py through DGS_SURFEL_LIB).
-#   here:        tools/ab_variants.sh build  name1:-DFOO=1 name2:"-DBAR=2 -DBAZ" ...     (writes gpurun_out/ab/lib_<name>.so ... no: csrc/ab_<name>.so, travels with the snapshot)
-#   on the box:  tools/ab_variants.sh run [quick_timing args]
+# Twin builds of the rasterizer library with other values of its -D tunables (DGS_BWD_CHUNK, DGS_BWD_MINWAVES, DGS_FWD_MINWAVES,
+# DGS_BIG_RECT), timed back to back on ONE lease (tools/quick_timing.py through DGS_SURFEL_LIB).
+#   where hipcc is:    tools/ab_variants.sh build  name1:-DDGS_BWD_CHUNK=64 name2:"-DDGS_BWD_CHUNK=32 -DDGS_BWD_MINWAVES=6" ...
+#                      (one library per name, ab_<name>.so next to the product library; earlier ab_*.so there are removed first)
+#   on the GPU box:    tools/ab_variants.sh run [quick_timing args]      (tools/ab_check.sh: the parity file first, then the timing)
 R=$(cd "$(dirname "$0")/.." && pwd)
 D=$R/dynamic-2dgs_amd/csrc
 if [ "$1" = build ]; then
@@ -9,7 +11,7 @@ if [ "$1" = build ]; then
   rm -f $D/ab_*.so
   for v in "$@"; do
     name=${v%%:*}; flags=${v#*:}
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -munsafe-fp-atomics -fno-slp-vectorize -DDGS_AB_BUILD $flags $D/surfel_rasterizer.hip -o $D/ab_$name.so 2>&1 | grep -v warning | grep -v "^$" &
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -munsafe-fp-atomics -fno-slp-vectorize $flags $D/surfel_rasterizer.hip -o $D/ab_$name.so 2>&1 | grep -v warning | grep -v "^$" &
   done
   wait
   ls $D/ab_*.so
