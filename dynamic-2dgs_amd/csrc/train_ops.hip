@@ -1,6 +1,7 @@
 // train_ops.hip -- the C entry points of libdgs_train_ops.so for gfx950 (include/dgs_train_ops.h): argument checks and
 // launches, nothing else.  The kernels live in one header per family:
 //   loss_kernels.h      SSIM / photometric loss, the regularisers, the merged loss forward, the loss combine
+//   metric_kernels.h    image metrics of an evaluation run: squared error, SSIM and MS-SSIM sums per plane, the pooled pyramid level
 //   knn_kernels.h       brute-force KNN and its two seeded refinements
 //   skinning_kernels.h  control-node skinning, forward and backward, and the reduces of its gradient tables
 //   step_kernels.h      step guard, view selection, flat Adam, densification statistics
@@ -15,6 +16,7 @@
 #include "../../include/dgs_train_ops.h"
 #include "knn_kernels.h"
 #include "loss_kernels.h"
+#include "metric_kernels.h"
 #include "node_mlp.h"
 #include "skinning_kernels.h"
 #include "step_kernels.h"
@@ -193,6 +195,51 @@ int dgs_loss_forward_merged(int C, int H, int W, const float* img, const float* 
     hipLaunchKernelGGL(loss_fwd_merged_kernel, dim3((unsigned)total), dim3(256), 0, (hipStream_t)stream, A, gauss(), (int)sg.x, (int)sg.y, C, a,
                        reg_partials, d_allmap, (int)rg.x, (int)rg.y);
     return launched("loss_fwd_merged_kernel");
+}
+
+// ---- image metrics of an evaluation run (metric_kernels.h) ----------------------------------------------------------------
+int dgs_image_metrics_layout(int out[3])
+{
+    if (!out) return fail(-1, "dgs_image_metrics_layout: NULL pointer");
+    out[0] = kTW; out[1] = kTH; out[2] = kMetricThreads;
+    return 0;
+}
+
+// 0 = same (H x W outputs, zero padding), 1 = valid ((H - 10) x (W - 10) outputs); the output domain, or false
+static bool metric_domain(int H, int W, int window, int* OH, int* OW)
+{
+    if (H < 1 || W < 1 || (window != 0 && window != 1)) return false;
+    *OH = window ? H - 2 * kR : H; *OW = window ? W - 2 * kR : W;
+    return *OH >= 1 && *OW >= 1;
+}
+
+size_t dgs_image_metrics_scratch_floats(int B, int C, int H, int W, int window)
+{
+    int OH, OW;
+    if (B < 1 || C < 1 || !metric_domain(H, W, window, &OH, &OW)) return 0;
+    const dim3 g = metric_grid(1, OH, OW);
+    return (size_t)B * C * g.x * g.y * 3;
+}
+
+int dgs_image_metrics(int B, int C, int H, int W, const float* pred, const float* gt, int window, int quantize, double* out,
+                      float* pooled_pred, float* pooled_gt, float* scratch, void* stream)
+{
+    if (B < 1 || C < 1 || (long long)B * C > 65535) return fail(-1, "dgs_image_metrics: B * C must be in [1, 65535] (grid z limit)");
+    if (H < 1 || W < 1) return fail(-1, "dgs_image_metrics: H and W must be at least 1");
+    if (window != 0 && window != 1) return fail(-1, "dgs_image_metrics: window must be 0 (same) or 1 (valid)");
+    int OH, OW;
+    if (!metric_domain(H, W, window, &OH, &OW)) return fail(-1, "dgs_image_metrics: the valid window needs H >= 11 and W >= 11");
+    if (!pred || !gt || !out || !scratch) return fail(-1, "dgs_image_metrics: NULL pointer");
+    if ((pooled_pred != nullptr) != (pooled_gt != nullptr)) return fail(-1, "dgs_image_metrics: pass both pooled planes or none");
+    if ((long long)H * W >= (1ll << 31)) return fail(-2, "dgs_image_metrics: plane too large for 32-bit offsets");
+    const dim3 grid = metric_grid(B * C, OH, OW);
+    if (grid.y > 65535) return fail(-2, "dgs_image_metrics: too many tile rows for the grid");
+    const MetricArgs A{H, W, OH, OW, window ? 0 : kR, quantize ? 1 : 0, pred, gt, scratch, pooled_pred, pooled_gt, (H + 1) / 2, (W + 1) / 2};
+    hipLaunchKernelGGL(image_metrics_kernel, grid, dim3(kMetricThreads), 0, (hipStream_t)stream, A, gauss());
+    if (int e = launched("image_metrics_kernel")) return e;
+    hipLaunchKernelGGL(image_metrics_combine_kernel, dim3(B * C), dim3(kMetricThreads), 0, (hipStream_t)stream, (const float*)scratch,
+                       (int)(grid.x * grid.y), out);
+    return launched("image_metrics_combine_kernel");
 }
 
 // ---- KNN ----------------------------------------------------------------------------------------------------------------

@@ -42,6 +42,10 @@ _SIGNATURES = {
     "dgs_regloss_fused_blocks": (_sz, [_ci, _ci]),
     "dgs_regloss_fused": (_ci, _REG + [_vp, _vp, _vp, _vp]),
     "dgs_loss_forward_merged": (_ci, [_ci, _ci, _ci] + [_vp] * 11 + [_cf, _cf, _vp, _vp, _vp, _vp]),
+    # image metrics of an evaluation run
+    "dgs_image_metrics_layout": (_ci, [_vp]),
+    "dgs_image_metrics_scratch_floats": (_sz, [_ci] * 5),
+    "dgs_image_metrics": (_ci, [_ci, _ci, _ci, _ci, _vp, _vp, _ci, _ci] + [_vp] * 5),
     # KNN
     "dgs_knn_points": (_ci, [_ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp]),
     "dgs_knn_points2": (_ci, _KNN2 + [_vp, _vp]),
@@ -84,8 +88,8 @@ _SIGNATURES = {
 
 def _deps():
     hdr = os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dgs_train_ops.h")
-    return [hdr] + [os.path.join(_CSRC, n) for n in ("train_ops.hip", "train_common.h", "step_kernels.h", "loss_kernels.h", "knn_kernels.h",
-                                                      "skinning_kernels.h", "node_mlp.h", "wave_reduce.h")]
+    return [hdr] + [os.path.join(_CSRC, n) for n in ("train_ops.hip", "train_common.h", "step_kernels.h", "loss_kernels.h", "metric_kernels.h",
+                                                      "knn_kernels.h", "skinning_kernels.h", "node_mlp.h", "wave_reduce.h")]
 
 
 def source_hash():
@@ -167,6 +171,36 @@ def fused_ssim(img1, img2):
     if img1.dim() != 3 or img1.shape != img2.shape or img1.dtype != torch.float32:
         raise RuntimeError("fused_ssim expects two fp32 [C,H,W] tensors of equal shape")
     return _FusedSSIM.apply(img1, img2.detach())
+
+
+def image_metrics_layout():
+    """(output tile width, output tile height, threads per workgroup) of the image-metrics kernel."""
+    out = (ctypes.c_int * 3)()
+    lib = load()
+    _check(lib, lib.dgs_image_metrics_layout(out), "dgs_image_metrics_layout")
+    return tuple(out)
+
+
+def image_metric_sums(pred, gt, window="same", quantize=False, pooled=False):
+    """dgs_image_metrics on two fp32 [B,C,H,W] HIP tensors -> (sums [B,C,3] float64 = (SE, S, CS) per plane, pooled_pred, pooled_gt);
+    the pooled planes [B,C,ceil(H/2),ceil(W/2)] are the next MS-SSIM level (None unless `pooled`).  window: "same" or "valid"."""
+    if pred.dim() != 4 or pred.shape != gt.shape or pred.dtype != torch.float32 or gt.dtype != torch.float32 or not pred.is_cuda or gt.device != pred.device:
+        raise RuntimeError("image_metric_sums expects two fp32 [B,C,H,W] tensors of equal shape on one HIP device")
+    if window not in ("same", "valid"):
+        raise ValueError("window must be 'same' or 'valid'")
+    lib = load()
+    a, b = pred.detach().contiguous(), gt.detach().contiguous()
+    B, C, H, W = a.shape
+    dev, win = a.device, int(window == "valid")
+    out = torch.empty((B, C, 3), dtype=torch.float64, device=dev)
+    scratch = torch.empty(max(int(lib.dgs_image_metrics_scratch_floats(B, C, H, W, win)), 1), dtype=torch.float32, device=dev)
+    pa = torch.empty((B, C, (H + 1) // 2, (W + 1) // 2), dtype=torch.float32, device=dev) if pooled else None
+    pb = torch.empty_like(pa) if pooled else None
+    with torch.cuda.device(dev):
+        rc = lib.dgs_image_metrics(B, C, H, W, a.data_ptr(), b.data_ptr(), win, int(bool(quantize)), out.data_ptr(),
+                                   pa.data_ptr() if pooled else None, pb.data_ptr() if pooled else None, scratch.data_ptr(), _stream(dev))
+    _check(lib, rc, "dgs_image_metrics")
+    return out, pa, pb
 
 
 def knn_indices(x, nodes, K):

@@ -313,6 +313,27 @@ int dgs_knn_refine(int N, int M, int D1, int D2, int K, const float* x1, const f
 int dgs_knn_refine_mode(int N, int M, int D1, int D2, int K, const float* x1, const float* x2, int x2_stride, const float* nodes,
                         long long* idx, int mode, void* stream);
 
+/* Image metrics of an evaluation run (the reference's render.py / metrics.py: PSNR, SSIM, MS-SSIM), for a batch pred, gt [B,C,H,W]
+ * in one launch plus a one-workgroup-per-plane combine.  With a, b one plane of pred, gt (after the optional quantisation), g the
+ * 11-tap sigma = 1.5 window of dgs_ssim_forward applied separably (11 x 11), C1 = 0.01^2, C2 = 0.03^2:
+ *   mu1 = g*a, mu2 = g*b, s11 = g*(a a) - mu1^2, s22 = g*(b b) - mu2^2, s12 = g*(a b) - mu1 mu2,
+ *   cs = (2 s12 + C2) / (s11 + s22 + C2),   ssim = (2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1) * cs
+ *   out[b][c] = { SE = sum (a - b)^2 over all H*W pixels,  S = sum ssim,  CS = sum cs  over the output domain }   (double [B,C,3])
+ * window 0 ("same"): the H x W domain with zero padding of 5 (utils/loss_utils.py ssim: what metrics.py reports);
+ * window 1 ("valid"): the (H - 10) x (W - 10) domain without padding (one level of MS-SSIM); needs H, W >= 11.
+ * quantize != 0: x <- floor(clamp(x, 0, 1) * 255 + 0.5) / 255 (every operation rounded in fp32) on both images as they are loaded:
+ * the 8-bit PNG round trip, so that the sums are those of the written files.
+ * pooled_pred, pooled_gt (both or neither): [B,C,ceil(H/2),ceil(W/2)], the next pyramid level of the (quantised) inputs:
+ * avg_pool2d(x, 2, padding=(H % 2, W % 2)), i.e. 2 x 2 windows at stride 2 behind one row / column of zeros on an odd axis, divisor 4.
+ * scratch: dgs_image_metrics_scratch_floats(B, C, H, W, window) floats (0 for sizes the call refuses), one slot of three per
+ * workgroup; the combine adds a plane's slots in float64 in a fixed order.  No atomics: a plane's three sums are bit-identical from
+ * run to run and do not depend on the rest of the batch.  B * C <= 65535.
+ * dgs_image_metrics_layout: out = {output tile width, output tile height, threads per workgroup} (what sizes a test should cover). */
+int dgs_image_metrics_layout(int out[3]);
+size_t dgs_image_metrics_scratch_floats(int B, int C, int H, int W, int window);
+int dgs_image_metrics(int B, int C, int H, int W, const float* pred, const float* gt, int window, int quantize, double* out,
+                      float* pooled_pred, float* pooled_gt, float* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
