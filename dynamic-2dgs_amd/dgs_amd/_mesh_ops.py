@@ -1,5 +1,6 @@
-"""ctypes binding of libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion, marching tetrahedra and the all-pairs nearest-neighbour
-and closest-triangle searches for gfx950, used by dgs_amd.mesh and dgs_amd.mesh_metrics when the data lives on a HIP device.  CPU tensors use the PyTorch /
+"""ctypes binding of libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion, marching tetrahedra, the all-pairs nearest-neighbour
+and closest-triangle searches and the z-buffer triangle rasterizer for gfx950, used by dgs_amd.mesh, dgs_amd.mesh_metrics and
+dgs_amd.mesh_render when the data lives on a HIP device.  CPU tensors use the PyTorch /
 NumPy statements in those modules."""
 import ctypes
 import os
@@ -15,7 +16,8 @@ LIB_PATH = os.path.join(_CSRC, "libdgs_mesh_ops.so")
 HIPCC_FLAGS = list(_ops.HIPCC_FLAGS) + ["-ffp-contract=off"]
 _lib = None
 _EXPORTS = ("dgs_mesh_ops_abi_version", "dgs_mesh_ops_last_error", "dgs_tsdf_integrate", "dgs_mt_classify", "dgs_mt_emit",
-            "dgs_nn_search", "dgs_nn_layout", "dgs_tri_search", "dgs_tri_layout")
+            "dgs_nn_search", "dgs_nn_layout", "dgs_tri_search", "dgs_tri_layout", "dgs_mesh_raster", "dgs_mesh_resolve",
+            "dgs_mesh_raster_layout")
 
 
 def _deps():
@@ -64,6 +66,12 @@ def load():
         lib.dgs_tri_search.argtypes = [ll, vp, ll, vp, ll, vp, vp]
         lib.dgs_tri_layout.restype = ci
         lib.dgs_tri_layout.argtypes = [ctypes.POINTER(ci)]
+        lib.dgs_mesh_raster.restype = ci
+        lib.dgs_mesh_raster.argtypes = [ll, vp, vp, ll, ci, ci, ci, vp, ci, vp]
+        lib.dgs_mesh_resolve.restype = ci
+        lib.dgs_mesh_resolve.argtypes = [ci, ci, vp, ll, vp, vp, ll, vp, ci, vp, vp, vp, vp, vp, vp]
+        lib.dgs_mesh_raster_layout.restype = ci
+        lib.dgs_mesh_raster_layout.argtypes = [ctypes.POINTER(ci)]
         if lib.dgs_mesh_ops_abi_version() != 2:
             raise RuntimeError("libdgs_mesh_ops.so ABI version mismatch (want 2, library says %d): rebuild it" % lib.dgs_mesh_ops_abi_version())
         _lib = lib
@@ -195,3 +203,64 @@ def closest_face(points, table, tri_chunk=None):
     _check(lib, rc, "dgs_tri_search")
     # the packed values are below 2^63 (d2 >= 0: sign bit clear), so the signed shift and mask are the unsigned ones
     return (best >> 32).to(torch.int32).view(torch.float32), best & 0xFFFFFFFF
+
+
+def raster_layout():
+    """(largest box area of the one-lane-per-face path, threads per workgroup, floats per table row, largest C) of dgs_mesh_raster."""
+    lib = load()
+    out = (ctypes.c_int * 4)()
+    _check(lib, lib.dgs_mesh_raster_layout(out), "dgs_mesh_raster_layout")
+    return tuple(int(v) for v in out)
+
+
+def raster(table, box, H, W, best=None):
+    """dgs_mesh_raster for every face of table [Nf,row] (mesh_render.raster_table) with a non-empty box [Nf,4] int32: the faces are
+    split by box area into the two paths' lists (a compare + nonzero) and each path is launched once, the first call clearing
+    `best`.  -> best [H*W] int64 (the packed minima; -1 = all-ones where nothing was drawn).  A `best` passed in is reused: it is
+    fully re-initialised."""
+    lib = load()
+    dev = table.device
+    layout = raster_layout()
+    _f32(table, "table")
+    if table.dim() != 2 or table.shape[1] != layout[2] or box.shape != (table.shape[0], 4) or box.dtype != torch.int32 or box.device != dev:
+        raise RuntimeError("raster: table [Nf,%d] fp32 and box [Nf,4] int32 on one device are expected" % layout[2])
+    if best is None:
+        best = torch.empty(H * W, dtype=torch.int64, device=dev)
+    elif not (best.is_cuda and best.device == dev and best.dtype == torch.int64 and best.is_contiguous() and best.numel() == H * W):
+        raise RuntimeError("raster: best must be a contiguous int64 tensor of H * W elements on the table's device")
+    b = box.long()
+    area = (b[:, 1] - b[:, 0] + 1).clamp(min=0) * (b[:, 3] - b[:, 2] + 1).clamp(min=0)
+    small = torch.nonzero((area > 0) & (area <= layout[0])).reshape(-1).to(torch.int32)
+    large = torch.nonzero(area > layout[0]).reshape(-1).to(torch.int32)
+    with torch.cuda.device(dev):
+        for path, lst, clear in ((0, small, 1), (1, large, 0)):
+            rc = lib.dgs_mesh_raster(table.shape[0], table.data_ptr(), lst.data_ptr() if lst.numel() else None, lst.numel(), path, H, W,
+                                     best.data_ptr(), clear, _stream(dev))
+            _check(lib, rc, "dgs_mesh_raster")
+    return best
+
+
+def resolve(best, table, faces, H, W, attr=None, background=None):
+    """dgs_mesh_resolve -> (face_id [H,W] int32, depth [H,W], bary [H,W,3], image [C,H,W] or None).  faces [Nf,3] int32; attr
+    [Nv,C] fp32 with background [C], or None for no image."""
+    lib = load()
+    dev = table.device
+    _f32(table, "table")
+    if not (faces.is_cuda and faces.dtype == torch.int32 and faces.is_contiguous() and faces.shape == (table.shape[0], 3)):
+        raise RuntimeError("resolve: faces must be a contiguous int32 HIP tensor [Nf,3]")
+    face_id = torch.empty((H, W), dtype=torch.int32, device=dev)
+    depth = torch.empty((H, W), dtype=torch.float32, device=dev)
+    bary = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+    C, image, nv = 0, None, 0
+    if attr is not None:
+        _f32(attr, "attr"), _f32(background, "background")
+        nv, C = attr.shape
+        if background.numel() != C:
+            raise RuntimeError("resolve: background must hold one value per channel")
+        image = torch.empty((C, H, W), dtype=torch.float32, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    with torch.cuda.device(dev):
+        rc = lib.dgs_mesh_resolve(H, W, best.data_ptr(), table.shape[0], ptr(table), ptr(faces), nv, ptr(attr), C, ptr(background),
+                                  face_id.data_ptr(), depth.data_ptr(), bary.data_ptr(), ptr(image), _stream(dev))
+    _check(lib, rc, "dgs_mesh_resolve")
+    return face_id, depth, bary, image

@@ -1,7 +1,7 @@
 /*
  * dgs_mesh_ops.h -- C ABI of the mesh kernels: depth-map fusion into a truncated signed distance volume, marching tetrahedra over
- * it, and the all-pairs nearest-neighbour and closest-triangle searches behind the geometry metrics of dgs_amd/mesh_metrics.py.
- * The first two replace the PyTorch / open3d path of the reference's render_mesh.py:
+ * it, the all-pairs nearest-neighbour and closest-triangle searches behind the geometry metrics of dgs_amd/mesh_metrics.py, and the
+ * z-buffer triangle rasterizer behind the mesh images of dgs_amd/mesh_render.py.  The first two replace the PyTorch / open3d path of the reference's render_mesh.py:
  *
  *   dgs_tsdf_integrate          <-  utils/mesh_utils.py:218-266  compute_sdf_perframe + compute_unbounded_tsdf (inv_contraction=None)
  *   dgs_mt_classify / _emit     <-  utils/mesh_utils.py:158-199 / :268-271  volume.extract_triangle_mesh() / marching_cubes_with_contraction
@@ -132,6 +132,74 @@ int dgs_tri_search(long long n_query, const float* query, long long n_tri, const
 
 /* out = {queries per workgroup, triangles per LDS round, default tri_chunk, floats per table row}. */
 int dgs_tri_layout(int out[4]);
+
+/* Z-buffer rasterizer of a triangle mesh: which face is nearest at every pixel centre, its depth, its barycentrics and the
+ * perspective-correct interpolation of per-vertex attributes -- the images of dgs_amd/mesh_render.py (the role nvdiffrast has in
+ * the reference's render_mesh.py:221-240).  Not differentiable.  Version 2 libraries from this commit on also carry the
+ * dgs_mesh_raster* / dgs_mesh_resolve calls; the version number is unchanged because nothing that existed before changes (the
+ * precedent of dgs_tri_*).  Every operation below is a separately rounded fp32 one (-ffp-contract=off), divisions, ceil and floor
+ * the IEEE ones; dgs_amd/mesh_render.py: raster_table / rasterize_torch / interpolate state the same arithmetic in PyTorch.
+ *
+ * VERTEX.  With m the camera's full_proj_transform as stored and p the vertex:
+ *   hom_c = p.x * m[0][c] + ((p.y * m[1][c] + p.z * m[2][c]) + m[3][c]) for c in {0, 1, 3}   (the expression of dgs_tsdf_integrate)
+ *   w = hom_3 (the view depth);   sx = ((hom_0 / w + 1) * W - 1) / 2,  sy likewise with H;   iw = 1 / w
+ * -- the rasterizer's pixel convention: the centre of pixel (i, j) is the screen point (i, j).
+ *
+ * FACE (v0, v1, v2).  Dropped if any corner has w <= near or a non-finite screen coordinate.  No clipping (a stated departure: the
+ * meshes of the protocol lie in front of the camera).  Edge k is the edge opposite corner k; its two endpoints are put in the
+ * canonical order a < b, lexicographic by screen coordinates (x, then y) -- vertex ids are not used -- and
+ *   e_k(P) = s_k * ((xb - xa) * (P.y - ya) - (yb - ya) * (P.x - xa)),   s_k = -1 if that order reversed the face's own order
+ *   (v_{k+1} to v_{k+2}), else +1.
+ * Two faces that share an edge compute the same number with opposite signs, welded or not: a pixel centre off the edge belongs to
+ * exactly one of them, one exactly on it to both; no crack between neighbours.  A = e_0(v0); a face with A == 0 (or NaN) is dropped.
+ * Pixel P = (i, j) is COVERED when it lies in the face's pixel box [ceil(min x), floor(max x)] x [ceil(min y), floor(max y)]
+ * intersected with the image, the three e_k are all >= 0 (A > 0) or all <= 0 (A < 0), S = (e_0 + e_1) + e_2 != 0 and, with
+ *   b_k = e_k / S;   q = (b_0 * iw_0 + b_1 * iw_1) + b_2 * iw_2;   z = 1 / q       (the perspective-correct view depth)
+ * q > 0: so z > 0, and a pixel whose q is NaN -- an edge function that overflowed to an infinity gives b = inf / inf -- is not covered.
+ * PIXEL.  best[P] = min over the covering faces of ((unsigned long long)bits(z) << 32 | face): the nearest face and, among equal
+ * depths, the lowest face index; all-ones where nothing covers P.  No back-face culling.
+ * ATTRIBUTES of the winning face (C channels per vertex, b and z recomputed by the same expressions):
+ *   a = (((b_0 * iw_0) * a_0 + (b_1 * iw_1) * a_1) + (b_2 * iw_2) * a_2) * z
+ *
+ * THE TABLE.  One row of 24 four-byte values per face = 96 bytes, a multiple of 16, computed once outside the kernels by
+ * elementwise PyTorch (raster_table); dgs_mesh_raster_layout reports the row length:
+ *    0.. 3   xa, ya, xb - xa, yb - ya of edge 0          4.. 7   of edge 1          8..11   of edge 2
+ *   12..15   s_0, s_1, s_2, sign of A (+1 / -1; 0 for a dropped face)
+ *   16..19   iw_0, iw_1, iw_2, one float of padding (never read into the arithmetic)
+ *   20..23   the pixel box x0, x1, y0, y1 as int32, already intersected with the image; (0, -1, 0, -1) for a dropped face or an
+ *            empty box
+ *
+ * dgs_mesh_raster: coverage of the faces named by `list` into best [H*W].  Two paths: path 0, one lane per face and a loop over its
+ * box, for faces of small boxes; path 1, one or more workgroups per face whose threads stride over the box, for large ones.  Both
+ * compute the same numbers and meet in `best` through the 64-bit atomic minimum (behind a plain load: the atomic is only issued
+ * when the candidate is smaller), so any face may go through either path and the result does not depend on the split; the caller
+ * puts the faces whose box holds at most dgs_mesh_raster_layout()[0] pixels on path 0 and leaves faces with an empty box out.
+ *   table [n_faces,24] 16-byte aligned;   list [n_list] int32 face indices (entries outside [0, n_faces) are skipped)
+ *   clear != 0: best is set to all-ones on `stream` first, so a second call with clear = 0 adds the other path's faces to the
+ *   same buffer.  n_list == 0 is legal: only the clear happens.
+ * No address can leave `best`: the kernels clamp every box to the image again before they form a pixel index.
+ * Refused with a negative status before any launch: H or W < 1, H * W > 2^30, n_faces < 0 or >= 2^31 (the face is the low 32 bits
+ * of the packed minimum), n_list < 0 or >= 2^31, a path other than 0 or 1, a null pointer with a non-zero count, a table that is
+ * not 16-byte aligned. */
+int dgs_mesh_raster(long long n_faces, const float* table, const int* list, long long n_list, int path, int H, int W,
+                    unsigned long long* best, int clear, void* stream);
+
+/* One thread per pixel: unpack best [H*W], recompute the winner's b and z and interpolate.  Outputs (any may be NULL and is then
+ * not written):
+ *   face_id [H*W] int32, -1 where nothing was drawn;   depth [H*W], 0 there;   bary [H*W,3], 0 there
+ *   image [C,H*W]: the interpolated attributes, background[c] where nothing was drawn
+ *   faces [n_faces,3] int32 vertex ids;  attr [n_vertices,C];  background [C] (device memory).  C in [0, 8]; with C == 0 the four
+ *   attribute arguments are not read.  A pixel whose packed face is not below n_faces counts as empty; a face that names a vertex
+ *   outside [0, n_vertices) gets the background.
+ * Refused with a negative status before any launch: H or W < 1, H * W > 2^30, n_faces or n_vertices < 0 or >= 2^31, C outside
+ * [0, 8], a null pointer with a non-zero count, a table that is not 16-byte aligned. */
+int dgs_mesh_resolve(int H, int W, const unsigned long long* best, long long n_faces, const float* table, const int* faces,
+                     long long n_vertices, const float* attr, int C, const float* background, int* face_id, float* depth, float* bary,
+                     float* image, void* stream);
+
+/* out = {largest box area (pixels) of path 0, threads per workgroup (both paths and the resolve), floats per table row,
+ *        largest C}: the sizes at which the code changes path. */
+int dgs_mesh_raster_layout(int out[4]);
 
 #ifdef __cplusplus
 }
