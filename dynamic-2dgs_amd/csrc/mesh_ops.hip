@@ -1,5 +1,6 @@
 // libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion of rendered depth maps, marching tetrahedra, the all-pairs
-// nearest-neighbour and closest-triangle searches of the mesh metrics and the z-buffer triangle rasterizer of the mesh images, gfx950.
+// nearest-neighbour and closest-triangle searches of the mesh metrics, the z-buffer triangle rasterizer of the mesh images and the
+// connected components of the mesh clean-up, gfx950.
 // Compiled with -ffp-contract=off: every fp32 operation below rounds on its own, which is what makes the result equal to the
 // PyTorch statement of the same arithmetic (dgs_amd/mesh.py) instead of close to it.
 #include <hip/hip_runtime.h>
@@ -526,6 +527,64 @@ __global__ __launch_bounds__(RAS_THREADS) void raster_resolve_kernel(int H, int 
         }
 }
 
+// ---- connected components -------------------------------------------------------------------------------------------------------
+// Lock-free union-find over label[] (include/dgs_mesh_ops.h states the contract).  INVARIANT: label[x] <= x at all times, and
+// label[x] is a node of x's component.  init writes label[x] = x; the only write of the hook kernel is a successful
+// atomicCAS(&label[hi], hi, lo) with lo < hi, which lowers the entry of a node that is a root at that instant; the compress kernel
+// only replaces an entry by the node's root.  So every walk x -> label[x] -> ... strictly descends and ends after at most x steps at
+// a node with label[r] == r.
+// STALE READS.  The walks read with relaxed agent-scope atomic loads, which are served past the CU's L1.  Correctness does not rest
+// on their freshness: whatever value a load returns was label[x] at some instant since the init launch, so it is an ancestor of x
+// (or x) in x's component.  A walk over stale values therefore ends at an ancestor r of its start that looked like a root; whether
+// it still is one is decided by the CAS alone, which executes at the memory side and returns the entry's true value.  If r has a
+// parent by then, the CAS fails, writes nothing and returns that parent (< r), and the union goes on from there: after every failed
+// CAS the larger of the two candidates is strictly smaller than before, so a thread cannot spin, however stale its loads are.
+constexpr int CC_THREADS = 256, CC_GROUPS_PER_THREAD = 1, CC_MAX_BLOCKS = 1 << 22;
+
+__device__ __forceinline__ int cc_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ __forceinline__ int cc_find(const int* label, int x) {          // 0 <= x < n_nodes; every value read is in [0, x]
+    for (int p = cc_load(label + x); p != x; p = cc_load(label + x)) x = p;
+    return x;
+}
+
+__device__ __forceinline__ void cc_unite(int* label, int a, int b) {
+    int ra = cc_find(label, a), rb = cc_find(label, b);
+    while (ra != rb) {                                                      // equal: a and b have a common ancestor already
+        const int hi = max(ra, rb), lo = min(ra, rb);
+        const int old = atomicCAS(label + hi, hi, lo);
+        if (old == hi) return;                                              // hi was a root and now hangs below lo
+        ra = cc_find(label, old), rb = lo;                                  // old < hi is hi's true parent: go on from there
+    }
+}
+
+__global__ __launch_bounds__(CC_THREADS) void cc_init_kernel(long long n_nodes, int* __restrict__ label) {
+    for (long long i = (long long)blockIdx.x * CC_THREADS + threadIdx.x; i < n_nodes; i += (long long)gridDim.x * CC_THREADS) label[i] = (int)i;
+}
+
+template <int K>
+__global__ __launch_bounds__(CC_THREADS) void cc_hook_kernel(long long n_nodes, const int* __restrict__ groups, long long n_groups, int* label) {
+    for (long long g = (long long)blockIdx.x * CC_THREADS + threadIdx.x; g < n_groups; g += (long long)gridDim.x * CC_THREADS) {
+        int anchor = -1;                                                    // the first id of the group that lies inside [0, n_nodes)
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            const int v = groups[g * K + j];
+            if (v < 0 || v >= n_nodes) continue;                            // index guard: no address below leaves label[0, n_nodes)
+            if (anchor < 0) anchor = v;
+            else if (v != anchor) cc_unite(label, anchor, v);
+        }
+    }
+}
+
+__global__ __launch_bounds__(CC_THREADS) void cc_compress_kernel(long long n_nodes, int* label) {
+    for (long long i = (long long)blockIdx.x * CC_THREADS + threadIdx.x; i < n_nodes; i += (long long)gridDim.x * CC_THREADS) {
+        const int p = cc_load(label + i);
+        if (p == (int)i) continue;
+        const int r = cc_find(label, p);
+        if (r != p) __hip_atomic_store(label + i, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 int check_raster(const char* what, int H, int W, long long n_faces, const float* table) {
     if (H < 1 || W < 1) return fail(-1, std::string(what) + ": H and W must be >= 1");
     if ((long long)H * W > (1LL << 30)) return fail(-1, std::string(what) + ": image too large (H * W > 2^30)");
@@ -695,6 +754,32 @@ int dgs_mesh_resolve(int H, int W, const unsigned long long* best, long long n_f
 int dgs_mesh_raster_layout(int out[4]) {
     if (!out) return fail(-1, "dgs_mesh_raster_layout: null pointer");
     out[0] = RAS_SMALL_AREA, out[1] = RAS_THREADS, out[2] = RAS_ROW, out[3] = RAS_MAX_C;
+    return 0;
+}
+
+int dgs_cc_labels(long long n_nodes, const int* groups, long long n_groups, int k, int* label, void* stream) {
+    if (k != 2 && k != 3) return fail(-1, "dgs_cc_labels: k must be 2 or 3");
+    if (n_nodes < 0 || n_groups < 0) return fail(-1, "dgs_cc_labels: negative count");
+    if (n_nodes >= (1LL << 31)) return fail(-1, "dgs_cc_labels: n_nodes must be below 2^31 (labels are int32)");
+    if ((n_nodes > 0 && !label) || (n_groups > 0 && !groups)) return fail(-1, "dgs_cc_labels: null pointer");
+    if (n_nodes == 0) return 0;
+    const long long per_block = (long long)CC_THREADS * CC_GROUPS_PER_THREAD;
+    auto blocks = [&](long long n) { const long long b = (n + per_block - 1) / per_block; return dim3((unsigned)(b > CC_MAX_BLOCKS ? CC_MAX_BLOCKS : b)); };
+    hipLaunchKernelGGL(cc_init_kernel, blocks(n_nodes), dim3(CC_THREADS), 0, (hipStream_t)stream, n_nodes, label);
+    if (int rc = launched("dgs_cc_labels (init)")) return rc;
+    if (n_groups == 0) return 0;
+    if (k == 2)
+        hipLaunchKernelGGL(cc_hook_kernel<2>, blocks(n_groups), dim3(CC_THREADS), 0, (hipStream_t)stream, n_nodes, groups, n_groups, label);
+    else
+        hipLaunchKernelGGL(cc_hook_kernel<3>, blocks(n_groups), dim3(CC_THREADS), 0, (hipStream_t)stream, n_nodes, groups, n_groups, label);
+    if (int rc = launched("dgs_cc_labels (hook)")) return rc;
+    hipLaunchKernelGGL(cc_compress_kernel, blocks(n_nodes), dim3(CC_THREADS), 0, (hipStream_t)stream, n_nodes, label);
+    return launched("dgs_cc_labels (compress)");
+}
+
+int dgs_cc_layout(int out[2]) {
+    if (!out) return fail(-1, "dgs_cc_layout: null pointer");
+    out[0] = CC_THREADS, out[1] = CC_GROUPS_PER_THREAD;
     return 0;
 }
 

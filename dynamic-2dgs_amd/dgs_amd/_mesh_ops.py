@@ -1,6 +1,6 @@
 """ctypes binding of libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion, marching tetrahedra, the all-pairs nearest-neighbour
-and closest-triangle searches and the z-buffer triangle rasterizer for gfx950, used by dgs_amd.mesh, dgs_amd.mesh_metrics and
-dgs_amd.mesh_render when the data lives on a HIP device.  CPU tensors use the PyTorch /
+and closest-triangle searches, the z-buffer triangle rasterizer and the connected components for gfx950, used by dgs_amd.mesh,
+dgs_amd.mesh_metrics, dgs_amd.mesh_render and dgs_amd.mesh_clean when the data lives on a HIP device.  CPU tensors use the PyTorch /
 NumPy statements in those modules."""
 import ctypes
 import os
@@ -17,7 +17,7 @@ HIPCC_FLAGS = list(_ops.HIPCC_FLAGS) + ["-ffp-contract=off"]
 _lib = None
 _EXPORTS = ("dgs_mesh_ops_abi_version", "dgs_mesh_ops_last_error", "dgs_tsdf_integrate", "dgs_mt_classify", "dgs_mt_emit",
             "dgs_nn_search", "dgs_nn_layout", "dgs_tri_search", "dgs_tri_layout", "dgs_mesh_raster", "dgs_mesh_resolve",
-            "dgs_mesh_raster_layout")
+            "dgs_mesh_raster_layout", "dgs_cc_labels", "dgs_cc_layout")
 
 
 def _deps():
@@ -72,6 +72,10 @@ def load():
         lib.dgs_mesh_resolve.argtypes = [ci, ci, vp, ll, vp, vp, ll, vp, ci, vp, vp, vp, vp, vp, vp]
         lib.dgs_mesh_raster_layout.restype = ci
         lib.dgs_mesh_raster_layout.argtypes = [ctypes.POINTER(ci)]
+        lib.dgs_cc_labels.restype = ci
+        lib.dgs_cc_labels.argtypes = [ll, vp, ll, ci, vp, vp]
+        lib.dgs_cc_layout.restype = ci
+        lib.dgs_cc_layout.argtypes = [ctypes.POINTER(ci)]
         if lib.dgs_mesh_ops_abi_version() != 2:
             raise RuntimeError("libdgs_mesh_ops.so ABI version mismatch (want 2, library says %d): rebuild it" % lib.dgs_mesh_ops_abi_version())
         _lib = lib
@@ -264,3 +268,35 @@ def resolve(best, table, faces, H, W, attr=None, background=None):
                                   face_id.data_ptr(), depth.data_ptr(), bary.data_ptr(), ptr(image), _stream(dev))
     _check(lib, rc, "dgs_mesh_resolve")
     return face_id, depth, bary, image
+
+
+def cc_layout():
+    """(threads per workgroup, groups per thread) of dgs_cc_labels: a workgroup takes their product of groups."""
+    lib = load()
+    out = (ctypes.c_int * 2)()
+    _check(lib, lib.dgs_cc_layout(out), "dgs_cc_layout")
+    return tuple(int(v) for v in out)
+
+
+def cc_labels(groups, n_nodes):
+    """dgs_cc_labels -> label [n_nodes] int32 on the device of groups [G,k] (int32, contiguous, k in {2, 3}): the smallest node id of
+    every node's component.  An id outside [0, n_nodes) is a ValueError (one aminmax, read on the host)."""
+    lib = load()
+    dev = groups.device
+    if not (groups.is_cuda and groups.dtype == torch.int32 and groups.is_contiguous()):
+        raise RuntimeError("cc_labels: a contiguous int32 HIP tensor is expected")
+    if groups.dim() != 2 or groups.shape[1] not in (2, 3):
+        raise RuntimeError("cc_labels: groups [G,2] or [G,3] are expected")
+    n_nodes = int(n_nodes)
+    if n_nodes < 0 or n_nodes >= 2 ** 31:
+        raise ValueError("cc_labels: n_nodes must be in [0, 2^31)")
+    if groups.shape[0]:
+        lo, hi = (int(x) for x in torch.stack(torch.aminmax(groups)).tolist())
+        if lo < 0 or hi >= n_nodes:
+            raise ValueError("cc_labels: node ids in [%d, %d] but n_nodes is %d" % (lo, hi, n_nodes))
+    label = torch.empty(n_nodes, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.dgs_cc_labels(n_nodes, groups.data_ptr() if groups.shape[0] else None, groups.shape[0], groups.shape[1],
+                               label.data_ptr() if n_nodes else None, _stream(dev))
+    _check(lib, rc, "dgs_cc_labels")
+    return label

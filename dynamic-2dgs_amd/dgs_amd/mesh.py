@@ -5,7 +5,8 @@ write frame_<i>.ply), without open3d / trimesh / mcubes.
   views_at_time            <- scene/__init__.py:120-131 getTrainCameras_mesh + utils/mesh_utils.py:94-155 reconstruction(state="mesh")
   TSDFVolume.integrate     <- utils/mesh_utils.py:218-266 compute_sdf_perframe + compute_unbounded_tsdf (inv_contraction=None)
   TSDFVolume.extract       <- the surface extraction of :158-199 / :268-271, here marching TETRAHEDRA (below)
-  keep_largest_components  <- utils/mesh_utils.py:24-45 post_process_mesh
+  keep_largest_components  <- utils/mesh_utils.py:24-45 post_process_mesh (on the host; mesh_clean.filter_components is the same
+                              rule on the mesh's own device, which extract_meshes uses for a mesh that lies on a HIP device)
   extract_meshes           <- render_mesh.py:169-219
 
 On a HIP device the fuser and the extraction are the kernels of libdgs_mesh_ops.so (include/dgs_mesh_ops.h, which states the
@@ -362,7 +363,11 @@ def extract_meshes(model_path, data_path, times=None, voxel_size=0.004, depth_tr
             depth, rgb, proj = views_at_time(surfels, deform, cams[s:s + view_chunk], t, bg, alpha_min=alpha_min, rasterizer_cls=rasterizer_cls)
             vol.integrate(depth, rgb, proj, trunc=trunc, depth_trunc=depth_trunc)
         v, f, c = vol.extract()
-        v, f, c = keep_largest_components(v, f, c, n_keep=n_keep, min_faces=min_faces)
+        if v.is_cuda:                                    # the same mesh, filtered where it lies: it leaves the device once, for the writer
+            from .mesh_clean import filter_components
+            v, f, c = filter_components(v, f, c, n_keep=n_keep, min_faces=min_faces)
+        else:
+            v, f, c = keep_largest_components(v, f, c, n_keep=n_keep, min_faces=min_faces)
         path = os.path.join(out_dir, "frame_{}.ply".format(i))
         dio.write_mesh_ply(path, v, f, c)
         written.append(path)

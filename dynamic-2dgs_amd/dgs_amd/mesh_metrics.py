@@ -324,11 +324,21 @@ def _flat(m):
 
 
 def evaluate_meshes(pred_dir, gt_dir, n_samples=100_000, seed=0, thresholds=(0.005, 0.01, 0.02), device="cuda:0", gt_transform=None, log=None,
-                    mode="samples"):
+                    mode="samples", clean_gt=False):
     """frame_<i>.ply of pred_dir against the i-th ground-truth mesh of gt_dir (its .obj / .ply files in natural sort order), for
     every i.  A different number of frames and ground-truth meshes is an error.  Writes <pred_dir>/mesh_metrics.json:
     {"frames": [{"frame": i, "pred": ..., "gt": ..., <metrics>}], "mean": {<metric>: mean over the frames}, "settings": ...} with
-    the per-threshold metrics flattened to 'fscore@0.01', and returns that dict.  mode: as in mesh_distance, recorded under "settings"."""
+    the per-threshold metrics flattened to 'fscore@0.01', and returns that dict.  mode: as in mesh_distance, recorded under "settings".
+    clean_gt: weld and clean every ground-truth mesh on load (mesh_clean.clean_mesh on `device`: an OBJ whose faces each carry their
+    own three vertices becomes an indexed mesh again, duplicated and degenerate triangles go); recorded under "settings" when set."""
+    def load_gt(path):
+        v, f = read_mesh(path)
+        if not clean_gt:
+            return v, f
+        from .mesh_clean import clean_mesh
+        v, f, _ = clean_mesh(torch.from_numpy(np.ascontiguousarray(v)).to(device), torch.from_numpy(np.ascontiguousarray(f)).to(device))
+        return v, f
+
     frames = {}
     for name in os.listdir(pred_dir):
         m = re.fullmatch(r"frame_(\d+)\.ply", name)
@@ -342,7 +352,7 @@ def evaluate_meshes(pred_dir, gt_dir, n_samples=100_000, seed=0, thresholds=(0.0
         raise ValueError("evaluate_meshes: no frame_<i>.ply in %s" % pred_dir)
     rows = []
     for i in range(len(gts)):
-        m = _flat(mesh_distance(read_mesh(os.path.join(pred_dir, frames[i])), read_mesh(os.path.join(gt_dir, gts[i])), n_samples=n_samples,
+        m = _flat(mesh_distance(read_mesh(os.path.join(pred_dir, frames[i])), load_gt(os.path.join(gt_dir, gts[i])), n_samples=n_samples,
                                 seed=seed, thresholds=thresholds, device=device, gt_transform=gt_transform, mode=mode))
         rows.append(dict({"frame": i, "pred": frames[i], "gt": gts[i]}, **m))
         if log is not None:
@@ -352,6 +362,8 @@ def evaluate_meshes(pred_dir, gt_dir, n_samples=100_000, seed=0, thresholds=(0.0
     result = {"frames": rows, "mean": {k: sum(r[k] for r in rows) / len(rows) for k in keys},
               "settings": {"n_samples": int(n_samples), "seed": int(seed), "thresholds": [float(t) for t in thresholds], "device": str(device),
                            "mode": mode, "gt_transform": None if gt_transform is None else np.asarray(gt_transform, dtype=np.float64).tolist()}}
+    if clean_gt:
+        result["settings"]["clean_gt"] = True
     with open(os.path.join(pred_dir, "mesh_metrics.json"), "w") as fh:
         json.dump(result, fh, indent=1)
     return result
@@ -369,9 +381,10 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--mode", choices=("samples", "surface"), default="samples",
                     help="samples: sample to nearest sample (carries the sampling floor); surface: sample to the other surface, exact")
+    ap.add_argument("--clean-gt", action="store_true", help="weld and clean the ground-truth meshes on load (dgs_amd.mesh_clean.clean_mesh)")
     a = ap.parse_args(argv)
     return evaluate_meshes(a.pred_dir, a.gt_dir, n_samples=a.samples, seed=a.seed, thresholds=tuple(a.thresholds), device=a.device, log=print,
-                           mode=a.mode)
+                           mode=a.mode, clean_gt=a.clean_gt)
 
 
 if __name__ == "__main__":

@@ -1,7 +1,8 @@
 /*
  * dgs_mesh_ops.h -- C ABI of the mesh kernels: depth-map fusion into a truncated signed distance volume, marching tetrahedra over
- * it, the all-pairs nearest-neighbour and closest-triangle searches behind the geometry metrics of dgs_amd/mesh_metrics.py, and the
- * z-buffer triangle rasterizer behind the mesh images of dgs_amd/mesh_render.py.  The first two replace the PyTorch / open3d path of the reference's render_mesh.py:
+ * it, the all-pairs nearest-neighbour and closest-triangle searches behind the geometry metrics of dgs_amd/mesh_metrics.py, the
+ * z-buffer triangle rasterizer behind the mesh images of dgs_amd/mesh_render.py, and the connected components behind
+ * dgs_amd/mesh_clean.py.  The first two replace the PyTorch / open3d path of the reference's render_mesh.py:
  *
  *   dgs_tsdf_integrate          <-  utils/mesh_utils.py:218-266  compute_sdf_perframe + compute_unbounded_tsdf (inv_contraction=None)
  *   dgs_mt_classify / _emit     <-  utils/mesh_utils.py:158-199 / :268-271  volume.extract_triangle_mesh() / marching_cubes_with_contraction
@@ -200,6 +201,48 @@ int dgs_mesh_resolve(int H, int W, const unsigned long long* best, long long n_f
 /* out = {largest box area (pixels) of path 0, threads per workgroup (both paths and the resolve), floats per table row,
  *        largest C}: the sizes at which the code changes path. */
 int dgs_mesh_raster_layout(int out[4]);
+
+/* Connected components of a graph given as groups of nodes: the primitive behind dgs_amd/mesh_clean.py (the component filter on the
+ * device, cluster_connected_triangles, clean_mesh -- the role open3d's cluster_connected_triangles has in the reference's
+ * utils/mesh_utils.py:24-45 and render_mesh_trajectory.py:41-88).  Version 2 libraries from this commit on also carry the dgs_cc_*
+ * pair; the version number is unchanged because nothing that existed before changes (the precedent of dgs_tri_* and
+ * dgs_mesh_raster*).
+ *   groups [n_groups,k] int32, k in {2, 3}: all nodes named by one group are in the same component.  The faces [F,3] of a mesh are
+ *     the k = 3 input as they stand (components over shared vertices); no edge list is materialised.  Repeated groups and groups
+ *     that name a node twice are legal.  An id outside [0, n_nodes) is skipped by an index guard (the rest of its group still
+ *     counts), so no address can leave `label`; the Python wrapper refuses such input.
+ *   label [n_nodes] int32: on return label[i] is the SMALLEST NODE ID of i's component; a node that no group names keeps its own id.
+ * The answer is unique, so it cannot depend on the order in which the atomics land: it is bit-identical from run to run and equal
+ * to the NumPy / PyTorch statement (dgs_amd/mesh_clean.py: component_labels on CPU tensors, dgs_amd/mesh.py: vertex_components).
+ *
+ * Three launches on `stream`, no host read between them:
+ *   init      label[i] = i
+ *   hook      lock-free union-find, a thread per group: for each of the k - 1 pairs (first node, other node) find both roots; while
+ *             they differ, atomicCAS(&label[hi], hi, lo) with hi the larger root.  A failed CAS writes nothing and returns hi's true
+ *             parent; the walk continues from there.
+ *   compress  label[i] = root(i), in place.
+ * INVARIANT: label[x] <= x at all times, and label[x] is a node of x's component.  Only a successful CAS lowers an entry during the
+ * hook, and only on a node that is a root at that instant (the compare value is the node's own id); the compress only replaces an
+ * entry by the same node's root.  Every walk x -> label[x] -> ... therefore strictly descends and ends at a node r with
+ * label[r] == r: every loop is finite.  When the hook has finished, each component is one tree (every pair of every group went
+ * through a successful CAS or was found under a common ancestor) and its root is its smallest node: the smallest node m has
+ * label[m] <= m inside its own component, hence label[m] == m.
+ * Memory scope.  The XCD L2s are not coherent with each other and a CU's L1 is never refreshed by another CU, so the walks use
+ * relaxed agent-scope atomic loads (32-bit, no inline assembly).  Correctness does not rest on their freshness: any value a load
+ * can return was the entry at some instant since the init launch, so it is an ancestor in the same component; a walk over stale
+ * values ends at an ancestor that merely looked like a root, and the CAS -- executed at the memory side on the true value --
+ * decides: it fails and hands back the true parent, and after each failed CAS the larger of the two candidates is strictly smaller
+ * than before.  The CAS result, not a load, ends the loop, so a load that stays stale for the whole launch cannot keep a thread
+ * spinning.
+ * The compress runs in place: no hook runs beside it, so the roots are fixed; a thread that meets a chain another thread has half
+ * compressed reads, per entry, either the old parent or the root, both ancestors on the way to the same root, and still ends there.
+ * Refused with a negative status before any launch: k outside {2, 3}, a negative count, n_nodes >= 2^31, a null pointer with a
+ * non-zero count.  n_nodes == 0 returns 0 and launches nothing; n_groups == 0 runs only the init. */
+int dgs_cc_labels(long long n_nodes, const int* groups, long long n_groups, int k, int* label, void* stream);
+
+/* out = {threads per workgroup, groups per thread}: a workgroup takes out[0] * out[1] groups -- the sizes at which the code changes
+ * path (a second workgroup, a ragged last one). */
+int dgs_cc_layout(int out[2]);
 
 #ifdef __cplusplus
 }
