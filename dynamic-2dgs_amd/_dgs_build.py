@@ -9,7 +9,11 @@ Several processes may ask for the same library at once (N ranks of a torchrun la
 temporary file in the same directory and the result is moved into place with `os.replace` (atomic on one file system), and
 the hash is recorded only after that -- a process that `dlopen`s the path sees either the old complete file or the new
 complete file, never a half-written one, and the ranks that waited for the lock find the hash current and reuse the binary.
+
+`NativeLibrary` is the one description of a library the bindings share: where it lives, what it is built from, its prototypes,
+and the life cycle from those (build, stale check, dlopen, prototypes, ABI check, error check).  No torch at import.
 """
+import ctypes
 import fcntl
 import hashlib
 import os
@@ -71,3 +75,75 @@ def build(lib_path, cmd, deps, flags, cwd, force=False, verbose=False):
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
     return lib_path, "compiled"
+
+
+def stream(device):
+    """The current HIP stream of `device` as the void* the C entry points take."""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+class NativeLibrary:
+    """default_path: where build() puts the library; `env` names an environment variable that may point load() at a caller's own
+    build instead.  inputs: the ORDERED list of files the hash covers (the order is part of the hash); `main` is the one handed to
+    the compiler.  signatures: {name: (restype, argtypes)} of every function of the public header.  abi: (function, wanted
+    version); last_error: the function check() reads the message from."""
+
+    def __init__(self, default_path, main, inputs, flags, signatures, abi, last_error, env=None, compiler=("hipcc",),
+                 missing="%s not found; build it with __graft_entry__.build()", failed="%s failed (%d): %s"):
+        self.default_path = default_path
+        self.path = os.environ.get(env, default_path) if env else default_path
+        self.main, self.inputs, self.flags, self.signatures = main, list(inputs), list(flags), signatures
+        (self.abi_fn, self.abi_version), self.last_error = abi, last_error
+        self.compiler, self.missing, self.failed = list(compiler), missing, failed
+        self._lib = None
+
+    def deps(self):
+        return list(self.inputs)
+
+    def source_hash(self):
+        """Hash of the sources + flags the library is built from (recorded next to the .so and with the PMC profiles)."""
+        return source_hash(self.inputs, self.flags)
+
+    def build(self, force=False, verbose=False):
+        """Compile the library in-tree at its default path.  Rebuilds whenever the hash of sources + flags differs from the one
+        recorded with the existing binary."""
+        cmd = self.compiler + self.flags + [self.main, "-o", self.default_path]
+        return build(self.default_path, cmd, self.inputs, self.flags, os.path.dirname(self.main), force=force, verbose=verbose)[0]
+
+    def _rebuild_if_stale(self):
+        """A binary built from other sources than the ones in the tree must never be what the tests or the bench measure: if the
+        hash recorded next to it differs from the hash of the current sources + flags, rebuild; if that is impossible, fail.
+        Only the default path is ours to judge: any other path is a caller's own build (an A/B build through `env`, or a twin
+        with its own flags) and the caller's responsibility."""
+        if os.path.abspath(self.path) != os.path.abspath(self.default_path):
+            return
+        have, want = recorded_hash(self.path), self.source_hash()
+        if have == want:
+            return
+        try:
+            self.build()
+        except Exception as ex:
+            raise RuntimeError("%s was built from other sources (recorded inputs %s, tree %s) and cannot be rebuilt here: %r"
+                               % (self.path, have, want, ex))
+
+    def load(self):
+        """dlopen the library and declare the prototypes of its public header."""
+        if self._lib is None:
+            if not os.path.exists(self.path):
+                raise RuntimeError(self.missing % self.path)
+            self._rebuild_if_stale()
+            lib = ctypes.CDLL(self.path)
+            for name, (restype, argtypes) in self.signatures.items():
+                f = getattr(lib, name)
+                f.restype, f.argtypes = restype, argtypes
+            have = getattr(lib, self.abi_fn)()
+            if have != self.abi_version:
+                raise RuntimeError("%s ABI version mismatch (want %d, library says %d): rebuild it"
+                                   % (os.path.basename(self.default_path), self.abi_version, have))
+            self._lib = lib
+        return self._lib
+
+    def check(self, rc, what):
+        if rc < 0:
+            raise RuntimeError(self.failed % (what, rc, getattr(self.load(), self.last_error)().decode("utf-8", "replace")))

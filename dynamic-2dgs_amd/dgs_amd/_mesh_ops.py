@@ -7,88 +7,54 @@ import os
 
 import torch
 
+import _dgs_build
 from . import _ops
 
 _CSRC = _ops._CSRC
-LIB_PATH = os.path.join(_CSRC, "libdgs_mesh_ops.so")
 # -ffp-contract=off: the fuser's accept / reject decisions sit on thresholds; with every operation rounded on its own the kernel
 # and the PyTorch statement of the same arithmetic take the same side of every one of them
 HIPCC_FLAGS = list(_ops.HIPCC_FLAGS) + ["-ffp-contract=off"]
-_lib = None
-_EXPORTS = ("dgs_mesh_ops_abi_version", "dgs_mesh_ops_last_error", "dgs_tsdf_integrate", "dgs_mt_classify", "dgs_mt_emit",
-            "dgs_nn_search", "dgs_nn_layout", "dgs_tri_search", "dgs_tri_layout", "dgs_mesh_raster", "dgs_mesh_resolve",
-            "dgs_mesh_raster_layout", "dgs_cc_labels", "dgs_cc_layout")
-
-
-def _deps():
-    hdr = os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dgs_mesh_ops.h")
-    return [os.path.join(_CSRC, "mesh_ops.hip"), hdr]
-
-
-def source_hash():
-    import _dgs_build
-    return _dgs_build.source_hash(_deps(), HIPCC_FLAGS)
-
-
-def build(force=False, verbose=False):
-    """hipcc, in-tree; rebuilt whenever the hash of sources + flags differs from the one recorded with the binary."""
-    import _dgs_build
-    cmd = ["hipcc"] + HIPCC_FLAGS + [os.path.join(_CSRC, "mesh_ops.hip"), "-o", LIB_PATH]
-    return _dgs_build.build(LIB_PATH, cmd, _deps(), HIPCC_FLAGS, _CSRC, force=force, verbose=verbose)[0]
+# name -> (restype, argtypes) of every function include/dgs_mesh_ops.h declares, grouped like csrc/mesh_ops.hip.  Written by hand:
+# tests/test_cabi_exports.py compares names, arities and return types with the header.
+_ci, _vp, _cf, _ll = ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_longlong
+_SEARCH = [_ll, _vp, _ll, _vp, _ll, _vp, _vp]         # n_query, query, n_set, set, chunk, best, stream
+_LAYOUT = [ctypes.POINTER(_ci)]
+_SIGNATURES = {
+    "dgs_mesh_ops_abi_version": (_ci, []),
+    "dgs_mesh_ops_last_error": (ctypes.c_char_p, []),
+    # fusion and marching tetrahedra
+    "dgs_tsdf_integrate": (_ci, [_ci, _ci, _ci, _cf, _cf, _cf, _cf, _ci, _ci, _ci, _vp, _vp, _vp, _cf, _cf, _cf, _ci, _vp, _vp, _vp, _vp]),
+    "dgs_mt_classify": (_ci, [_ci, _ci, _ci] + [_vp] * 6),
+    "dgs_mt_emit": (_ci, [_ci, _ci, _ci, _cf, _cf, _cf, _cf, _vp, _vp, _ll, _vp, _vp, _vp, _ll] + [_vp] * 7),
+    # the two searches
+    "dgs_nn_search": (_ci, _SEARCH),
+    "dgs_nn_layout": (_ci, _LAYOUT),
+    "dgs_tri_search": (_ci, _SEARCH),
+    "dgs_tri_layout": (_ci, _LAYOUT),
+    # triangle rasterizer
+    "dgs_mesh_raster": (_ci, [_ll, _vp, _vp, _ll, _ci, _ci, _ci, _vp, _ci, _vp]),
+    "dgs_mesh_resolve": (_ci, [_ci, _ci, _vp, _ll, _vp, _vp, _ll, _vp, _ci] + [_vp] * 6),
+    "dgs_mesh_raster_layout": (_ci, _LAYOUT),
+    # connected components
+    "dgs_cc_labels": (_ci, [_ll, _vp, _ll, _ci, _vp, _vp]),
+    "dgs_cc_layout": (_ci, _LAYOUT),
+}
+_SOURCES = ["mesh_ops.hip", "mesh_common.h", "mesh_fusion_kernels.h", "mesh_search_kernels.h", "mesh_raster_kernels.h", "mesh_cc_kernels.h"]
+_LIB = _dgs_build.NativeLibrary(
+    os.path.join(_CSRC, "libdgs_mesh_ops.so"), os.path.join(_CSRC, _SOURCES[0]),
+    [os.path.join(_CSRC, n) for n in _SOURCES] + [os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dgs_mesh_ops.h")],
+    HIPCC_FLAGS, _SIGNATURES, ("dgs_mesh_ops_abi_version", 2), "dgs_mesh_ops_last_error")
+LIB_PATH = _LIB.path
+_deps, source_hash, build, load = _LIB.deps, _LIB.source_hash, _LIB.build, _LIB.load
+_stream = _dgs_build.stream
 
 
 def exported_symbols():
-    return _EXPORTS
-
-
-def load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError("%s not found; build it with __graft_entry__.build()" % LIB_PATH)
-        from diff_surfel_rasterization._C import _refuse_stale
-        _refuse_stale(LIB_PATH, source_hash, build)   # never run a binary built from other sources than the tree's
-        lib = ctypes.CDLL(LIB_PATH)
-        vp, ci, cf, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_longlong
-        lib.dgs_mesh_ops_abi_version.restype = ci
-        lib.dgs_mesh_ops_last_error.restype = ctypes.c_char_p
-        lib.dgs_tsdf_integrate.restype = ci
-        lib.dgs_tsdf_integrate.argtypes = [ci, ci, ci, cf, cf, cf, cf, ci, ci, ci, vp, vp, vp, cf, cf, cf, ci, vp, vp, vp, vp]
-        lib.dgs_mt_classify.restype = ci
-        lib.dgs_mt_classify.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp]
-        lib.dgs_mt_emit.restype = ci
-        lib.dgs_mt_emit.argtypes = [ci, ci, ci, cf, cf, cf, cf, vp, vp, ll, vp, vp, vp, ll, vp, vp, vp, vp, vp, vp, vp]
-        lib.dgs_nn_search.restype = ci
-        lib.dgs_nn_search.argtypes = [ll, vp, ll, vp, ll, vp, vp]
-        lib.dgs_nn_layout.restype = ci
-        lib.dgs_nn_layout.argtypes = [ctypes.POINTER(ci)]
-        lib.dgs_tri_search.restype = ci
-        lib.dgs_tri_search.argtypes = [ll, vp, ll, vp, ll, vp, vp]
-        lib.dgs_tri_layout.restype = ci
-        lib.dgs_tri_layout.argtypes = [ctypes.POINTER(ci)]
-        lib.dgs_mesh_raster.restype = ci
-        lib.dgs_mesh_raster.argtypes = [ll, vp, vp, ll, ci, ci, ci, vp, ci, vp]
-        lib.dgs_mesh_resolve.restype = ci
-        lib.dgs_mesh_resolve.argtypes = [ci, ci, vp, ll, vp, vp, ll, vp, ci, vp, vp, vp, vp, vp, vp]
-        lib.dgs_mesh_raster_layout.restype = ci
-        lib.dgs_mesh_raster_layout.argtypes = [ctypes.POINTER(ci)]
-        lib.dgs_cc_labels.restype = ci
-        lib.dgs_cc_labels.argtypes = [ll, vp, ll, ci, vp, vp]
-        lib.dgs_cc_layout.restype = ci
-        lib.dgs_cc_layout.argtypes = [ctypes.POINTER(ci)]
-        if lib.dgs_mesh_ops_abi_version() != 2:
-            raise RuntimeError("libdgs_mesh_ops.so ABI version mismatch (want 2, library says %d): rebuild it" % lib.dgs_mesh_ops_abi_version())
-        _lib = lib
-    return _lib
+    return tuple(_SIGNATURES)
 
 
 def _check(lib, rc, what):
-    if rc < 0:
-        raise RuntimeError("%s failed (%d): %s" % (what, rc, lib.dgs_mesh_ops_last_error().decode()))
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _LIB.check(rc, what)
 
 
 def _f32(t, what):
@@ -153,68 +119,60 @@ def marching_tetrahedra(dims, origin, voxel, tsdf, weight, color=None):
     return vertices, faces, colors
 
 
+def _layout(name, n):
+    lib = load()
+    out = (ctypes.c_int * n)()
+    _check(lib, getattr(lib, name)(out), name)
+    return tuple(int(v) for v in out)
+
+
+def _search(who, entry, layout, chunk, query, qname, ref, rname, cols, expected):
+    """nearest and closest_face: device and dtype checks, the chunk default (layout[2]), the `best` buffer, the call and the
+    unpacking of the packed minimum."""
+    lib = load()
+    dev = query.device
+    _f32(query, qname), _f32(ref, rname)
+    if ref.device != dev:
+        raise RuntimeError("%s: %s lives on another device than %s" % (who, rname, qname))
+    if query.dim() != 2 or query.shape[1] != 3 or ref.dim() != 2 or ref.shape[1] != cols:
+        raise RuntimeError("%s: %s are expected" % (who, expected))
+    chunk = layout[2] if chunk is None else int(chunk)
+    best = torch.empty(query.shape[0], dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = getattr(lib, entry)(query.shape[0], query.data_ptr(), ref.shape[0], ref.data_ptr(), chunk, best.data_ptr(), _stream(dev))
+    _check(lib, rc, entry)
+    # the packed values are below 2^63 (d2 >= 0: sign bit clear), so the signed shift and mask are the unsigned ones
+    return (best >> 32).to(torch.int32).view(torch.float32), best & 0xFFFFFFFF
+
+
 def nn_layout():
     """(queries per workgroup, reference points per LDS round, default ref_chunk) of dgs_nn_search."""
-    lib = load()
-    out = (ctypes.c_int * 3)()
-    _check(lib, lib.dgs_nn_layout(out), "dgs_nn_layout")
-    return tuple(int(v) for v in out)
+    return _layout("dgs_nn_layout", 3)
 
 
 def nearest(query, ref, ref_chunk=None):
     """dgs_nn_search: (d2 [Nq] f32, idx [Nq] int64) of the nearest point of ref [Nr,3] for every point of query [Nq,3]; equal
     distances go to the lowest index.  The result does not depend on ref_chunk (default: nn_layout()[2])."""
-    lib = load()
-    dev = query.device
-    _f32(query, "query"), _f32(ref, "ref")
-    if ref.device != dev:
-        raise RuntimeError("nearest: ref lives on another device than query")
-    if query.dim() != 2 or query.shape[1] != 3 or ref.dim() != 2 or ref.shape[1] != 3:
-        raise RuntimeError("nearest: query [Nq,3] and ref [Nr,3] are expected")
-    chunk = nn_layout()[2] if ref_chunk is None else int(ref_chunk)
-    best = torch.empty(query.shape[0], dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.dgs_nn_search(query.shape[0], query.data_ptr(), ref.shape[0], ref.data_ptr(), chunk, best.data_ptr(), _stream(dev))
-    _check(lib, rc, "dgs_nn_search")
-    # the packed values are below 2^63 (d2 >= 0: sign bit clear), so the signed shift and mask are the unsigned ones
-    return (best >> 32).to(torch.int32).view(torch.float32), best & 0xFFFFFFFF
+    return _search("nearest", "dgs_nn_search", nn_layout(), ref_chunk, query, "query", ref, "ref", 3, "query [Nq,3] and ref [Nr,3]")
 
 
 def tri_layout():
     """(queries per workgroup, triangles per LDS round, default tri_chunk, floats per table row) of dgs_tri_search."""
-    lib = load()
-    out = (ctypes.c_int * 4)()
-    _check(lib, lib.dgs_tri_layout(out), "dgs_tri_layout")
-    return tuple(int(v) for v in out)
+    return _layout("dgs_tri_layout", 4)
 
 
 def closest_face(points, table, tri_chunk=None):
     """dgs_tri_search: (d2 [Nq] f32, face [Nq] int64) of the closest triangle of table [Nf,row] (mesh_metrics.triangle_table) for
     every point of points [Nq,3]; equal distances go to the lowest face.  The result does not depend on tri_chunk (default:
     tri_layout()[2])."""
-    lib = load()
-    dev = points.device
-    _f32(points, "points"), _f32(table, "table")
-    if table.device != dev:
-        raise RuntimeError("closest_face: table lives on another device than points")
     layout = tri_layout()
-    if points.dim() != 2 or points.shape[1] != 3 or table.dim() != 2 or table.shape[1] != layout[3]:
-        raise RuntimeError("closest_face: points [Nq,3] and table [Nf,%d] are expected" % layout[3])
-    chunk = layout[2] if tri_chunk is None else int(tri_chunk)
-    best = torch.empty(points.shape[0], dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.dgs_tri_search(points.shape[0], points.data_ptr(), table.shape[0], table.data_ptr(), chunk, best.data_ptr(), _stream(dev))
-    _check(lib, rc, "dgs_tri_search")
-    # the packed values are below 2^63 (d2 >= 0: sign bit clear), so the signed shift and mask are the unsigned ones
-    return (best >> 32).to(torch.int32).view(torch.float32), best & 0xFFFFFFFF
+    return _search("closest_face", "dgs_tri_search", layout, tri_chunk, points, "points", table, "table", layout[3],
+                   "points [Nq,3] and table [Nf,%d]" % layout[3])
 
 
 def raster_layout():
     """(largest box area of the one-lane-per-face path, threads per workgroup, floats per table row, largest C) of dgs_mesh_raster."""
-    lib = load()
-    out = (ctypes.c_int * 4)()
-    _check(lib, lib.dgs_mesh_raster_layout(out), "dgs_mesh_raster_layout")
-    return tuple(int(v) for v in out)
+    return _layout("dgs_mesh_raster_layout", 4)
 
 
 def raster(table, box, H, W, best=None):
@@ -272,10 +230,7 @@ def resolve(best, table, faces, H, W, attr=None, background=None):
 
 def cc_layout():
     """(threads per workgroup, groups per thread) of dgs_cc_labels: a workgroup takes their product of groups."""
-    lib = load()
-    out = (ctypes.c_int * 2)()
-    _check(lib, lib.dgs_cc_layout(out), "dgs_cc_layout")
-    return tuple(int(v) for v in out)
+    return _layout("dgs_cc_layout", 2)
 
 
 def cc_labels(groups, n_nodes):

@@ -3,14 +3,13 @@ gfx950, used by dgs_amd.losses / dgs_amd.deform when their inputs live on a HIP 
 the PyTorch formulation (that is what the CPU tests and bench.py's cpu_baseline leg run)."""
 import ctypes
 import os
-import subprocess
 
 import torch
 
+import _dgs_build
+
 _CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
-LIB_PATH = os.environ.get("DGS_TRAIN_OPS_LIB", os.path.join(_CSRC, "libdgs_train_ops.so"))  # override: development A/B builds only
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-slp-vectorize", "-munsafe-fp-atomics"]
-_lib = None
 # name -> (restype, argtypes) of every function include/dgs_train_ops.h declares, grouped like csrc/train_ops.hip.  Written by hand:
 # tests/test_cabi_exports.py compares names and arities with the header.
 _ci, _vp, _cf, _ll, _sz = ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_longlong, ctypes.c_size_t
@@ -86,52 +85,24 @@ _SIGNATURES = {
 }
 
 
-def _deps():
-    hdr = os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dgs_train_ops.h")
-    return [hdr] + [os.path.join(_CSRC, n) for n in ("train_ops.hip", "train_common.h", "step_kernels.h", "loss_kernels.h", "metric_kernels.h",
-                                                      "knn_kernels.h", "skinning_kernels.h", "node_mlp.h", "wave_reduce.h")]
-
-
-def source_hash():
-    import _dgs_build
-    return _dgs_build.source_hash(_deps(), HIPCC_FLAGS)
-
-
-def build(force=False, verbose=False):
-    """hipcc, in-tree; rebuilt whenever the hash of sources + flags differs from the one recorded with the binary."""
-    import _dgs_build
-    cmd = ["hipcc"] + HIPCC_FLAGS + [os.path.join(_CSRC, "train_ops.hip"), "-o", LIB_PATH]
-    return _dgs_build.build(LIB_PATH, cmd, _deps(), HIPCC_FLAGS, _CSRC, force=force, verbose=verbose)[0]
+_SOURCES = ["train_ops.hip", "train_common.h", "step_kernels.h", "loss_kernels.h", "metric_kernels.h", "knn_kernels.h", "skinning_kernels.h",
+            "node_mlp.h", "wave_reduce.h"]
+_LIB = _dgs_build.NativeLibrary(
+    os.path.join(_CSRC, "libdgs_train_ops.so"), os.path.join(_CSRC, _SOURCES[0]),
+    [os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dgs_train_ops.h")] + [os.path.join(_CSRC, n) for n in _SOURCES],
+    HIPCC_FLAGS, _SIGNATURES, ("dgs_train_ops_abi_version", 3), "dgs_train_ops_last_error",
+    env="DGS_TRAIN_OPS_LIB")  # override: development A/B builds only
+LIB_PATH = _LIB.path
+_deps, source_hash, build, load = _LIB.deps, _LIB.source_hash, _LIB.build, _LIB.load
+_stream = _dgs_build.stream
 
 
 def exported_symbols():
     return tuple(_SIGNATURES)
 
 
-def load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError("%s not found; build it with __graft_entry__.build()" % LIB_PATH)
-        from diff_surfel_rasterization._C import _refuse_stale
-        _refuse_stale(LIB_PATH, source_hash, build)   # never run a binary built from other sources than the tree's
-        lib = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in _SIGNATURES.items():
-            f = getattr(lib, name)
-            f.restype, f.argtypes = restype, argtypes
-        if lib.dgs_train_ops_abi_version() != 3:
-            raise RuntimeError("libdgs_train_ops.so ABI version mismatch (want 3, library says %d): rebuild it" % lib.dgs_train_ops_abi_version())
-        _lib = lib
-    return _lib
-
-
 def _check(lib, rc, what):
-    if rc < 0:
-        raise RuntimeError("%s failed (%d): %s" % (what, rc, lib.dgs_train_ops_last_error().decode()))
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _LIB.check(rc, what)
 
 
 class _FusedSSIM(torch.autograd.Function):

@@ -12,152 +12,73 @@ import ctypes
 import os
 import torch
 
+import _dgs_build
+
 _CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
-LIB_NAME = "libdgs_surfel_rasterizer.so"
-LIB_PATH = os.environ.get("DGS_SURFEL_LIB", os.path.join(_CSRC, LIB_NAME))  # override: development A/B builds only
 # -fno-slp-vectorize: hipcc's SLP pass packs adjacent fp32 ops into v_pk_*_f32, which on gfx950 cost twice the cycles
 # of the scalar forms (no throughput gain) plus v_mov shuffles to pair the operands; measured -17 % / -19 % on the
 # forward / backward blend kernels without it.
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-fno-slp-vectorize"]
 _SOURCES = ["surfel_rasterizer.hip", "kernels_blend.h", "kernels_preprocess.h", "surfel_math.h", "wave_reduce.h"]
+_INPUTS = [os.path.join(_CSRC, s) for s in _SOURCES] + [os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dgs_surfel_rasterizer.h")]
 
 _ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
-_lib = None
-
-_EXPORTS = ("dgs_abi_version", "dgs_last_error", "dgs_rasterizer_mark_visible", "dgs_rasterizer_forward",
-            "dgs_rasterizer_backward", "dgs_debug_layout", "dgs_set_tight_rects", "dgs_set_option", "dgs_read_overflow", "dgs_profile_enable", "dgs_profile_reset",
-            "dgs_profile_read", "dgs_set_overflow_flag", "dgs_context_create", "dgs_context_destroy", "dgs_context_set_option",
-            "dgs_context_set_overflow_flag", "dgs_context_read_overflow", "dgs_context_profile_enable", "dgs_context_profile_reset",
-            "dgs_context_profile_read", "dgs_context_forward", "dgs_context_backward", "dgs_get_option", "dgs_context_get_option")
-
-
-def _deps():
-    hdr = os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dgs_surfel_rasterizer.h")
-    return [os.path.join(_CSRC, s) for s in _SOURCES] + [hdr]
-
-
-def source_hash():
-    """Hash of the sources + flags the library is built from (recorded next to the .so and with the PMC profiles)."""
-    import _dgs_build
-    return _dgs_build.source_hash(_deps(), HIPCC_FLAGS)
-
-
-def build(force=False, verbose=False):
-    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Rebuilds whenever the hash of
-    sources + flags differs from the one recorded with the existing binary."""
-    import _dgs_build
-    cmd = ["hipcc"] + HIPCC_FLAGS + [os.path.join(_CSRC, "surfel_rasterizer.hip"), "-o", LIB_PATH]
-    return _dgs_build.build(LIB_PATH, cmd, _deps(), HIPCC_FLAGS, _CSRC, force=force, verbose=verbose)[0]
-
-
-PRECISE_LIB_PATH = os.path.join(_CSRC, "libdgs_surfel_rasterizer_precise.so")
-
-
-def build_precise(force=False, verbose=False):
-    """Test-only twin of the library with -DDGS_PRECISE_MATH: IEEE division and expf() instead of v_rcp_f32 / v_exp_f32 in
-    the per-pixel arithmetic (surfel_math.h fast_rcp / fast_exp).  tests/test_precise_math_gpu.py loads it in a subprocess
-    (DGS_SURFEL_LIB) to show how much of the distance to the oracle the fast intrinsics account for; never the product."""
-    import _dgs_build
-    flags = HIPCC_FLAGS + ["-DDGS_PRECISE_MATH"]
-    cmd = ["hipcc"] + flags + [os.path.join(_CSRC, "surfel_rasterizer.hip"), "-o", PRECISE_LIB_PATH]
-    return _dgs_build.build(PRECISE_LIB_PATH, cmd, _deps(), flags, _CSRC, force=force, verbose=verbose)[0]
+# name -> (restype, argtypes) of every function include/dgs_surfel_rasterizer.h declares, grouped like csrc/surfel_rasterizer.hip.
+# Written by hand: tests/test_cabi_exports.py compares names, arities and return types with the header.
+_ci, _vp, _cf, _sz, _dp = ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_size_t, ctypes.POINTER(ctypes.c_double)
+_FWD = [_ALLOC_FN, _vp, _ALLOC_FN, _vp, _ALLOC_FN, _vp, _ci, _ci, _ci, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _cf, _vp, _vp, _vp, _vp, _vp,
+        _cf, _cf, _ci, _vp, _vp, _vp, _ci, _vp]
+_BWD = [_ci, _ci, _ci, _ci, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _cf, _vp, _vp, _vp, _vp, _vp, _cf, _cf] + [_vp] * 15 + [_ci, _vp]
+_SIGNATURES = {
+    "dgs_abi_version": (_ci, []),
+    "dgs_last_error": (ctypes.c_char_p, []),
+    # contexts
+    "dgs_context_create": (_vp, []),
+    "dgs_context_destroy": (None, [_vp]),
+    "dgs_context_set_option": (_ci, [_vp, _ci, _ci]),
+    "dgs_context_get_option": (_ci, [_vp, _ci]),
+    "dgs_context_set_overflow_flag": (_ci, [_vp, _vp]),
+    "dgs_context_read_overflow": (_ci, [_vp, _ci]),
+    "dgs_context_profile_enable": (_ci, [_vp, _ci]),
+    "dgs_context_profile_reset": (None, [_vp]),
+    "dgs_context_profile_read": (_ci, [_vp, _dp, _ci]),
+    "dgs_context_forward": (_ci, [_vp] + _FWD),
+    "dgs_context_backward": (_ci, [_vp] + _BWD),
+    # the reference-shaped surface: the default context of the current device
+    "dgs_rasterizer_mark_visible": (_ci, [_ci, _vp, _vp, _vp, _vp, _vp]),
+    "dgs_rasterizer_forward": (_ci, _FWD),
+    "dgs_rasterizer_backward": (_ci, _BWD),
+    "dgs_debug_layout": (_ci, [_ci, _ci, _ci, _ci, _ci, ctypes.POINTER(_sz), _ci]),
+    "dgs_set_tight_rects": (None, [_ci]),
+    "dgs_set_option": (_ci, [_ci, _ci]),
+    "dgs_get_option": (_ci, [_ci]),
+    "dgs_set_overflow_flag": (_ci, [_vp]),
+    "dgs_read_overflow": (_ci, [_ci]),
+    "dgs_profile_enable": (None, [_ci]),
+    "dgs_profile_reset": (None, []),
+    "dgs_profile_read": (_ci, [_dp, _ci]),
+}
 
 
-def _refuse_stale(lib_path, hash_fn, build_fn):
-    """A binary built from other sources than the ones in the tree must never be what the tests or the bench measure: if the
-    hash recorded next to it differs from the hash of the current sources + flags, rebuild; if that is impossible, fail."""
-    import _dgs_build
-    if os.path.basename(lib_path) not in (LIB_NAME, "libdgs_train_ops.so", "libdgs_mesh_ops.so") or os.path.dirname(os.path.abspath(lib_path)) != os.path.abspath(_CSRC):
-        return   # DGS_SURFEL_LIB override: an explicit A/B or twin build (its own flags), the caller's responsibility
-    have, want = _dgs_build.recorded_hash(lib_path), hash_fn()
-    if have == want:
-        return
-    try:
-        build_fn()
-    except Exception as ex:
-        raise RuntimeError("%s was built from other sources (recorded inputs %s, tree %s) and cannot be rebuilt here: %r"
-                           % (lib_path, have, want, ex))
+def _library(name, flags, env=None):
+    return _dgs_build.NativeLibrary(
+        os.path.join(_CSRC, name), _INPUTS[0], _INPUTS, flags, _SIGNATURES, ("dgs_abi_version", 3), "dgs_last_error", env=env,
+        missing="%s not found: the MI355X surfel rasterizer has no CPU fallback. Build it with "
+                "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).", failed="%s failed (status %d): %s")
 
 
-def load():
-    """dlopen the library and declare the prototypes of include/dgs_surfel_rasterizer.h."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            "%s not found: the MI355X surfel rasterizer has no CPU fallback. Build it with "
-            "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc)." % LIB_PATH)
-    _refuse_stale(LIB_PATH, source_hash, build)
-    lib = ctypes.CDLL(LIB_PATH)
-    vp, ci, cf, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
-    lib.dgs_abi_version.restype = ci
-    lib.dgs_abi_version.argtypes = []
-    lib.dgs_last_error.restype = ctypes.c_char_p
-    lib.dgs_last_error.argtypes = []
-    lib.dgs_rasterizer_mark_visible.restype = ci
-    lib.dgs_rasterizer_mark_visible.argtypes = [ci, vp, vp, vp, vp, vp]
-    fwd_args = [_ALLOC_FN, vp, _ALLOC_FN, vp, _ALLOC_FN, vp, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp,
-                cf, cf, ci, vp, vp, vp, ci, vp]
-    bwd_args = [ci, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                vp, vp, vp, vp, vp, ci, vp]
-    lib.dgs_rasterizer_forward.restype = ci
-    lib.dgs_rasterizer_forward.argtypes = fwd_args
-    lib.dgs_rasterizer_backward.restype = ci
-    lib.dgs_rasterizer_backward.argtypes = bwd_args
-    lib.dgs_context_forward.restype = ci
-    lib.dgs_context_forward.argtypes = [vp] + fwd_args
-    lib.dgs_context_backward.restype = ci
-    lib.dgs_context_backward.argtypes = [vp] + bwd_args
-    lib.dgs_context_create.restype = vp
-    lib.dgs_context_create.argtypes = []
-    lib.dgs_context_destroy.restype = None
-    lib.dgs_context_destroy.argtypes = [vp]
-    lib.dgs_context_set_option.restype = ci
-    lib.dgs_context_set_option.argtypes = [vp, ci, ci]
-    lib.dgs_context_get_option.restype = ci
-    lib.dgs_context_get_option.argtypes = [vp, ci]
-    lib.dgs_get_option.restype = ci
-    lib.dgs_get_option.argtypes = [ci]
-    lib.dgs_context_set_overflow_flag.restype = ci
-    lib.dgs_context_set_overflow_flag.argtypes = [vp, vp]
-    lib.dgs_context_read_overflow.restype = ci
-    lib.dgs_context_read_overflow.argtypes = [vp, ci]
-    lib.dgs_context_profile_enable.restype = ci
-    lib.dgs_context_profile_enable.argtypes = [vp, ci]
-    lib.dgs_context_profile_reset.restype = None
-    lib.dgs_context_profile_reset.argtypes = [vp]
-    lib.dgs_context_profile_read.restype = ci
-    lib.dgs_context_profile_read.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ci]
-    lib.dgs_set_overflow_flag.restype = ci
-    lib.dgs_set_overflow_flag.argtypes = [vp]
-    lib.dgs_debug_layout.restype = ci
-    lib.dgs_debug_layout.argtypes = [ci, ci, ci, ci, ci, ctypes.POINTER(sz), ci]
-    lib.dgs_set_tight_rects.restype = None
-    lib.dgs_set_tight_rects.argtypes = [ci]
-    lib.dgs_set_option.restype = ci
-    lib.dgs_set_option.argtypes = [ci, ci]
-    lib.dgs_read_overflow.restype = ci
-    lib.dgs_read_overflow.argtypes = [ci]
-    lib.dgs_profile_enable.restype = None
-    lib.dgs_profile_enable.argtypes = [ci]
-    lib.dgs_profile_reset.restype = None
-    lib.dgs_profile_reset.argtypes = []
-    lib.dgs_profile_read.restype = ci
-    lib.dgs_profile_read.argtypes = [ctypes.POINTER(ctypes.c_double), ci]
-    if lib.dgs_abi_version() != 3:
-        raise RuntimeError("libdgs_surfel_rasterizer.so ABI version mismatch")
-    _lib = lib
-    return lib
+_LIB = _library("libdgs_surfel_rasterizer.so", HIPCC_FLAGS, env="DGS_SURFEL_LIB")  # override: development A/B builds only
+# Test-only twin of the library with -DDGS_PRECISE_MATH: IEEE division and expf() instead of v_rcp_f32 / v_exp_f32 in the per-pixel
+# arithmetic (surfel_math.h fast_rcp / fast_exp).  tests/test_precise_math_gpu.py loads it in a subprocess (DGS_SURFEL_LIB) to show
+# how much of the distance to the oracle the fast intrinsics account for; never the product.
+_PRECISE = _library("libdgs_surfel_rasterizer_precise.so", HIPCC_FLAGS + ["-DDGS_PRECISE_MATH"])
+LIB_PATH, PRECISE_LIB_PATH = _LIB.path, _PRECISE.path
+_deps, source_hash, build, load, build_precise = _LIB.deps, _LIB.source_hash, _LIB.build, _LIB.load, _PRECISE.build
+_stream = _dgs_build.stream
 
 
 def exported_symbols():
-    return _EXPORTS
-
-
-def _raise(lib, code, where):
-    msg = lib.dgs_last_error().decode("utf-8", "replace")
-    raise RuntimeError("%s failed (status %d): %s" % (where, code, msg))
+    return tuple(_SIGNATURES)
 
 
 def _need_device(**tensors):
@@ -194,10 +115,6 @@ class _Resizer:
             return 0
 
 
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 class Context:
     """An explicit library context (dgs_context_create): its own options, overflow flag, staging word and timing state.
     The operator surface uses the per-device default context; a caller that drives one device from several threads, or wants
@@ -213,21 +130,18 @@ class Context:
     def set_option(self, key, value):
         lib = load()
         rc = lib.dgs_context_set_option(self.handle, int(key), int(value))
-        if rc < 0:
-            _raise(lib, rc, "context.set_option")
+        _LIB.check(rc, "context.set_option")
 
     def get_option(self, key):
         lib = load()
         v = lib.dgs_context_get_option(self.handle, int(key))
-        if v < 0:
-            _raise(lib, v, "context.get_option")
+        _LIB.check(v, "context.get_option")
         return int(v)
 
     def set_overflow_flag(self, tensor):
         lib = load()
         rc = lib.dgs_context_set_overflow_flag(self.handle, None if tensor is None else tensor.data_ptr())
-        if rc < 0:
-            _raise(lib, rc, "context.set_overflow_flag")
+        _LIB.check(rc, "context.set_overflow_flag")
         self._flag = tensor   # keep it alive
 
     def read_overflow(self, reset=True):
@@ -280,8 +194,7 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
                 _ptr(col), _ptr(opa), _ptr(sc), float(scale_modifier), _ptr(rot), _ptr(tm), _ptr(vm), _ptr(pm), _ptr(cp),
                 float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), out_color.data_ptr(), out_others.data_ptr(),
                 radii.data_ptr(), int(bool(debug)), _stream(dev))
-        if rendered < 0:
-            _raise(lib, rendered, "rasterize_gaussians")
+        _LIB.check(rendered, "rasterize_gaussians")
     return rendered, out_color, out_others, radii, geom.tensor, binning.tensor, img.tensor
 
 
@@ -331,8 +244,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 dL_dcolors.data_ptr() if want_colors else None, dL_dmeans3D.data_ptr(), dL_dtransMat.data_ptr() if want_transmat else None,
                 _ptr(dL_dsh), dL_dscales.data_ptr(),
                 dL_drotations.data_ptr(), int(bool(debug)), _stream(dev))
-        if rc < 0:
-            _raise(lib, rc, "rasterize_gaussians_backward")
+        _LIB.check(rc, "rasterize_gaussians_backward")
     return (dL_dmeans2D, dL_dcolors if want_colors else None, dL_dopacity, dL_dmeans3D, dL_dtransMat if want_transmat else None, dL_dsh,
             dL_dscales, dL_drotations)
 
@@ -347,8 +259,7 @@ def mark_visible(means3D, viewmatrix, projmatrix):
         m3, vm, pm = _f32c(means3D), _f32c(viewmatrix), _f32c(projmatrix)
         with torch.cuda.device(means3D.device):
             rc = lib.dgs_rasterizer_mark_visible(P, _ptr(m3), _ptr(vm), _ptr(pm), present.data_ptr(), _stream(means3D.device))
-        if rc < 0:
-            _raise(lib, rc, "mark_visible")
+        _LIB.check(rc, "mark_visible")
     return present
 
 
@@ -358,8 +269,7 @@ def debug_layout(which, P=0, width=1, height=1, R=0):
     lib = load()
     buf = (ctypes.c_size_t * 8)()
     n = lib.dgs_debug_layout(int(which), int(P), int(width), int(height), int(R), buf, 8)
-    if n < 0:
-        _raise(lib, n, "debug_layout")
+    _LIB.check(n, "debug_layout")
     return [int(buf[i]) for i in range(n)]
 
 
@@ -388,8 +298,7 @@ def set_option(key, value, device=None):
     lib = load()
     with _on(device):
         rc = lib.dgs_set_option(int(key), int(value))
-    if rc < 0:
-        _raise(lib, rc, "set_option")
+    _LIB.check(rc, "set_option")
 
 
 def get_option(key, device=None):
@@ -397,8 +306,7 @@ def get_option(key, device=None):
     lib = load()
     with _on(device):
         v = lib.dgs_get_option(int(key))
-    if v < 0:
-        _raise(lib, v, "get_option")
+    _LIB.check(v, "get_option")
     return int(v)
 
 
@@ -427,8 +335,7 @@ def set_overflow_flag(tensor, device=None):
     else:
         with _on(device):
             rc = lib.dgs_set_overflow_flag(None)
-    if rc < 0:
-        _raise(lib, rc, "set_overflow_flag")
+    _LIB.check(rc, "set_overflow_flag")
     idx = torch.cuda.current_device() if device is None else torch.device(device).index
     idx = torch.cuda.current_device() if idx is None else idx
     if tensor is None:

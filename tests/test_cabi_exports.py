@@ -99,13 +99,17 @@ def _prototypes(header):
     return out
 
 
-def test_binding_table_matches_header_arity():
-    """Every prototype of dgs_train_ops.h has a table entry with as many argtypes as the prototype has parameters and the restype of
-    its return type: ctypes passes a call of the wrong arity without complaint."""
-    table = _ops_module()._SIGNATURES
-    protos = _prototypes("dgs_train_ops.h")
-    assert sorted(protos) == declared_functions("dgs_train_ops.h")
-    restypes = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p}
+@pytest.mark.parametrize("module,header", [("dgs_amd._ops", "dgs_train_ops.h"), ("diff_surfel_rasterization._C", "dgs_surfel_rasterizer.h"),
+                                           ("dgs_amd._mesh_ops", "dgs_mesh_ops.h")], ids=["train_ops", "rasterizer", "mesh_ops"])
+def test_binding_table_matches_header_arity(module, header):
+    """Every prototype of a library's header has a table entry with as many argtypes as the prototype has parameters and the restype
+    of its return type, and the table has no other entry: ctypes passes a call of the wrong arity without complaint."""
+    table = _binding_module(module)._SIGNATURES
+    protos = _prototypes(header)
+    assert sorted(protos) == declared_functions(header)
+    assert sorted(table) == declared_functions(header)
+    restypes = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p, "void": None, "void *": ctypes.c_void_p,
+                "dgs_context *": ctypes.c_void_p}   # (an opaque handle)
     wrong = []
     for name, (ret, nargs) in sorted(protos.items()):
         restype, argtypes = table[name]
