@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define DGS_HD __host__ __device__ __forceinline__
 #else
 #define DGS_HD inline

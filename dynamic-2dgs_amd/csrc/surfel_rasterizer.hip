@@ -1,6 +1,8 @@
 // surfel_rasterizer.hip -- host orchestration + C ABI (include/dgs_surfel_rasterizer.h) of the
 // MI355X surfel rasterizer.  Stage order follows CudaRasterizer::Rasterizer::forward / backward
-// (rasterizer_impl.cu:198-342, :346-448 of the reference); everything runs on the caller's stream.
+// (rasterizer_impl.cu:198-342, :346-448 of the reference); everything runs on the caller's stream.  An entry point validates its
+// arguments, reads the context's options once (Options) and runs one function per stage over what the stages share (Pass); the
+// kernels are in the *_kernels.h files, one family each.
 //
 // State.  The reference's entry points are stateless and re-entrant across devices.  Everything this
 // library adds on top (tile-list policy, capacity mode and its overflow flag, the pinned word of the one device->host
@@ -16,8 +18,12 @@
 #include <vector>
 
 #include "../../include/dgs_surfel_rasterizer.h"
-#include "kernels_blend.h"
-#include "kernels_preprocess.h"
+#include "binning_kernels.h"
+#include "blend_bwd_kernels.h"
+#include "blend_fwd_kernels.h"
+#include "surfel_kernels.h"
+#include "tile_order_kernels.h"
+#include "tile_sort_kernels.h"
 
 namespace {
 
@@ -36,13 +42,13 @@ int fail(int code, const std::string& msg)
             return fail(DGS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));             \
     } while (0)
 
-// CHECK_CUDA equivalent (auxiliary.h:271-278): with debug, synchronise after the stage
-#define DGS_STAGE(name, debug, stream)                                                                 \
-    do {                                                                                               \
-        hipError_t e__ = hipGetLastError();                                                            \
-        if (e__ == hipSuccess && (debug)) e__ = hipStreamSynchronize(stream);                          \
-        if (e__ != hipSuccess) return fail(DGS_ERR_HIP, std::string(name) + ": " + hipGetErrorString(e__)); \
-    } while (0)
+// CHECK_CUDA equivalent (auxiliary.h:271-278), the end of every stage: with debug, synchronise after it
+int stage_done(const char* name, int debug, hipStream_t stream)
+{
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && debug) e = hipStreamSynchronize(stream);
+    return e == hipSuccess ? 0 : fail(DGS_ERR_HIP, std::string(name) + ": " + hipGetErrorString(e));
+}
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -56,6 +62,11 @@ struct Carver {  // 128-byte aligned sub-allocation, like obtain() in rasterizer
         return o;
     }
 };
+
+// The three scratch buffers.  A layout holds the byte offsets of a buffer's sub-arrays (dgs_debug_layout hands them to the tests);
+// a view is the same buffer as typed pointers, built once per call from (layout, base): the forward writes through it what the
+// backward reads through it.
+template <class T> void bind(T*& p, char* base, size_t off) { p = (T*)(base + off); }
 
 struct GeomLayout {
     size_t rec, total, internal_radii, acc, rects, bytes;
@@ -73,15 +84,24 @@ struct GeomLayout {
     }
 };
 
+struct GeomView {
+    float4* rec; uint32_t* state; int* internal_radii; float* acc; uint2* rects;   // state[3]: BlendFwdArgs::clean_flag
+    GeomView(const GeomLayout& l, char* b) { bind(rec, b, l.rec); bind(state, b, l.total); bind(internal_radii, b, l.internal_radii); bind(acc, b, l.acc); bind(rects, b, l.rects); }
+};
+
 struct ImageLayout {
     size_t final_T, n_contrib, ranges, tile_last, order_fwd, order_bwd, group_xcd, tile_counts, cursor, long_thr, bytes;
     bool lds_bins;  // per-workgroup LDS histograms fit (T * 4 bytes <= 144 KB)
     int tiles_x, tiles_y, ntiles;
+    int off_blocks;      // workgroups of the column passes and of bin_offsets_kernel: 64 tiles each
+    size_t hist_bytes;   // one LDS histogram: a counter per tile
     ImageLayout(int W, int H)
     {
         tiles_x = (W + dgs::kTileX - 1) / dgs::kTileX;
         tiles_y = (H + dgs::kTileY - 1) / dgs::kTileY;
         ntiles = tiles_x * tiles_y;
+        off_blocks = (ntiles + 63) / 64;
+        hist_bytes = (size_t)ntiles * 4;
         Carver c;
         const size_t plane = (size_t)ntiles * dgs::kTilePix;
         final_T = c.take(3 * plane * 4);
@@ -93,12 +113,22 @@ struct ImageLayout {
         order_bwd = c.take(order_len * 4);
         group_xcd = c.take((size_t)dgs::kOrderMaxGroups * 4);   // tile order 4: the forward's group -> XCD map, reused by the backward
         // global-atomics path: the T tile counts; LDS-histogram path: the 2 ceil(T / 64) + 1 words bin_offsets_kernel's workgroups meet in
-        tile_counts = c.take((size_t)(ntiles > 2 * ((ntiles + 63) / 64) + 1 ? ntiles : 2 * ((ntiles + 63) / 64) + 1) * 4);
-        lds_bins = (size_t)ntiles * 4 <= 144 * 1024;
+        tile_counts = c.take((size_t)(ntiles > 2 * off_blocks + 1 ? ntiles : 2 * off_blocks + 1) * 4);
+        lds_bins = hist_bytes <= 144 * 1024;
         // LDS path: G x T matrix of per-workgroup counts / cursors; fallback: T global cursors
         cursor = c.take(lds_bins ? (size_t)dgs::kBinGroups * ntiles * 4 : (size_t)ntiles * 4);
         long_thr = c.take(sizeof(dgs::LongThr));   // thresholds of the long-tile path (forward: scan_tiles_kernel, backward: prep_bwd_kernel)
         bytes = align_up(c.off, 128);
+    }
+};
+
+struct ImageView {
+    float* final_T; uint2* ranges; dgs::LongThr* long_thr;
+    uint32_t *n_contrib, *tile_last, *order_fwd, *order_bwd, *group_xcd, *tile_counts, *cursor;
+    ImageView(const ImageLayout& l, char* b)
+    {
+        bind(final_T, b, l.final_T); bind(n_contrib, b, l.n_contrib); bind(ranges, b, l.ranges); bind(tile_last, b, l.tile_last); bind(order_fwd, b, l.order_fwd);
+        bind(order_bwd, b, l.order_bwd); bind(group_xcd, b, l.group_xcd); bind(tile_counts, b, l.tile_counts); bind(cursor, b, l.cursor); bind(long_thr, b, l.long_thr);
     }
 };
 
@@ -115,6 +145,12 @@ struct BinningLayout {
         scratch = c.take(with_scratch ? 2 * n * 8 : 8);
         bytes = align_up(c.off, 128);
     }
+};
+
+struct BinningView {
+    uint32_t* point_list = nullptr; uint64_t *keys = nullptr, *scratch = nullptr;
+    BinningView() {}   // no binning buffer: a backward with R == 0
+    BinningView(const BinningLayout& l, char* b) { bind(point_list, b, l.point_list); bind(keys, b, l.keys); bind(scratch, b, l.scratch); }
 };
 
 dgs::Camera make_camera(const float* view_dev, const float* campos_dev, int W, int H, float tan_fovx, float tan_fovy)
@@ -194,40 +230,51 @@ struct HostStage {
     }
 };
 
-}  // namespace
-
-struct dgs_context {
-    dgs_context()
-    {
-        if (const char* e = getenv("DGS_LONG_TILES")) long_tiles.store(atoi(e) != 0);   // A/B runs of whole programs (bench.py, the test suite)
-        if (const char* e = getenv("DGS_MERGED_OFFSETS")) merged_offsets.store(atoi(e) != 0);
-        if (const char* e = getenv("DGS_ORDER_RIDER")) order_rider.store(atoi(e) != 0);
-        if (const char* e = getenv("DGS_ACC_RIDER")) acc_rider.store(atoi(e) != 0);
-    }
-    int device = 0;
-    std::atomic<int> tight_rects{1};  // exact opacity-aware tile rectangles (surfel_math.h tight_tile_rect)
-    std::atomic<int> sort_regs{2};    // per-tile sort: 2 LSD radix in LDS (default), 1 bitonic network in registers, 0 bitonic in LDS
-    std::atomic<int> tile_order{3};   // kernels_blend.h tile_for_block (3 = longest tile first)
-    std::atomic<int> deterministic{0};   // key 7: 1 backward blend without atomics, fixed summation order (tests); 2 fixed-point integer atomics
-    unsigned long long* acc64 = nullptr; // key 7 = 2: [P, kAccFloats] fixed-point accumulator rows, zero between backward passes
-    size_t acc64_rows = 0;
-    std::vector<unsigned long long*> acc64_retired;   // outgrown rows: a captured graph may still point at them, freed with the context
-    std::atomic<int> sh_all_rows{0};     // key 8: dL_dsh written for every row (zeros for culled surfels / unused bands)
-    std::atomic<int> long_tiles{1};      // key 9: four workgroups (one per quadrant, four list quarters each) for the longest tiles
+// The options of a context (dgs_set_option in the public header says what each does), one row per key, in key order: default, accepted
+// range (or "any value, stored as 0 / 1") and the environment variable that overrides the default -- for A/B runs of whole programs
+// (bench.py, the test suite).
+struct OptionSpec { int key, def, lo, hi; bool boolean; const char* env; };
+constexpr int kIntMax = 0x7fffffff;
+constexpr OptionSpec kOptions[DGS_OPT_COUNT] = {
+    {DGS_OPT_TIGHT_RECTS, 1, 0, 1, true, nullptr},       // exact opacity-aware tile rectangles (surfel_math.h tight_tile_rect)
+    {DGS_OPT_TILE_ORDER, 3, 0, 4, false, nullptr},       // blend_common.h tile_for_block (3 = longest tile first)
+    {DGS_OPT_CAPACITY, 0, 0, kIntMax, false, nullptr},   // > 0: capacity mode (no host read of num_rendered; stream-capture safe)
+    {DGS_OPT_TILE_SORT, 2, 0, 2, false, nullptr},        // per-tile sort: 2 LSD radix in LDS, 1 bitonic network in registers, 0 bitonic in LDS
+    {DGS_OPT_GRID_LIMIT_BWD, 0, 0, kIntMax, false, nullptr},   // > 0 (diagnostic): the backward blend processes only the first N tiles of its dispatch order
+    {DGS_OPT_GRID_LIMIT_FWD, 0, 0, kIntMax, false, nullptr},   // > 0 (diagnostic): same for the forward blend (the other tiles' state is zero-filled)
+    {DGS_OPT_LIST_HINT, 0, 0, kIntMax, false, nullptr},  // capacity mode: promised longest tile list; 0 = no promise (every sort kernel is launched)
+    {DGS_OPT_DETERMINISTIC, 0, 0, 2, false, nullptr},    // 1 backward blend without atomics, fixed summation order (tests); 2 fixed-point integer atomics
+    {DGS_OPT_SH_ALL_ROWS, 0, 0, 1, true, nullptr},       // dL_dsh written for every row (zeros for culled surfels / unused bands)
+    {DGS_OPT_LONG_TILES, 1, 0, 1, true, "DGS_LONG_TILES"},   // four workgroups (one per quadrant, four list quarters each) for the longest tiles
     // Measured (tools/diag/long_tune.py, blend fwd / bwd in ms; uniform 200k scene | ONE densified scene, 88 k surfels, kept as a checkpoint):
     //   path off 0.127 / 0.264 | 0.140 / 0.358;  forward divisor 150: 0.124 | 0.139, 400: .. | 0.130, 800: 0.125 | 0.131, 1600: .. | 0.131,
     //   3200: 0.133 | ..;  backward divisor 256: .. | 0.331, 512: 0.253 | 0.280, 1024: 0.259 | 0.281, 2048: .. | 0.283.
     // The backward of a densified scene is as long as its longest tiles and gains 22 %; its forward is closer to throughput-bound and
     // gains 7 %; an opaque knot (40 k of 100 k surfels on a few tiles) pays 2-4 % for the forward path (0.112 -> 0.114-0.116).
-    std::atomic<int> long_div_fwd{400};  // key 10: a list is long from num_rendered / this (and 768 entries) on
-    std::atomic<int> long_div_bwd{512};  // key 11: a tile is long from (sum of traversed lengths) / this (and 512 entries) on
-    std::atomic<int> order_rider{1};     // key 13: capacity mode: tile_last + the forward's dispatch order by a rider workgroup of the scatter launch (0: by bin_offsets_kernel's last workgroup)
-    std::atomic<int> merged_offsets{1};  // key 12: tile counts -> ranges, bucket cursors and dispatch order in one launch (bin_offsets_kernel); 0 = column pass, scan, column pass
-    std::atomic<int> capacity{0};     // > 0: capacity mode (no host read of num_rendered; stream-capture safe)
-    std::atomic<int> list_hint{0};    // capacity mode (key 6): promised longest tile list; 0 = no promise (every sort kernel is launched)
-    std::atomic<int> grid_limit_bwd{0};   // > 0 (diagnostic, key 4): the backward blend processes only the first N tiles of its dispatch order
-    std::atomic<bool> acc_rider{true};    // key 14: the forward blend zeroes the backward's accumulator rows (BlendFwdArgs::clear)
-    std::atomic<int> grid_limit_fwd{0};   // > 0 (diagnostic, key 5): same for the forward blend (the other tiles' state is zero-filled)
+    {DGS_OPT_LONG_DIV_FWD, 400, 1, kIntMax, false, nullptr},   // a list is long from num_rendered / this (and 768 entries) on
+    {DGS_OPT_LONG_DIV_BWD, 512, 1, kIntMax, false, nullptr},   // a tile is long from (sum of traversed lengths) / this (and 512 entries) on
+    {DGS_OPT_MERGED_OFFSETS, 1, 0, 1, true, "DGS_MERGED_OFFSETS"},   // tile counts -> ranges, bucket cursors and dispatch order in one launch (bin_offsets_kernel); 0 = column pass, scan, column pass
+    {DGS_OPT_ORDER_RIDER, 1, 0, 1, true, "DGS_ORDER_RIDER"},   // capacity mode: tile_last + the forward's dispatch order by a rider workgroup of the scatter launch (0: by bin_offsets_kernel's last workgroup)
+    {DGS_OPT_ACC_RIDER, 1, 0, 1, true, "DGS_ACC_RIDER"},       // the forward blend zeroes the backward's accumulator rows (BlendFwdArgs::clear)
+};
+constexpr bool options_in_key_order(int k = 0) { return k == DGS_OPT_COUNT || (kOptions[k].key == k && options_in_key_order(k + 1)); }
+static_assert(options_in_key_order(), "kOptions is indexed by key");
+
+}  // namespace
+
+struct dgs_context {
+    dgs_context()
+    {
+        for (const OptionSpec& o : kOptions) {
+            const char* e = o.env ? getenv(o.env) : nullptr;
+            opt[o.key].store(e ? atoi(e) != 0 : o.def);
+        }
+    }
+    int device = 0;
+    std::atomic<int> opt[DGS_OPT_COUNT];   // by key (kOptions)
+    unsigned long long* acc64 = nullptr; // DGS_OPT_DETERMINISTIC = 2: [P, kAccFloats] fixed-point accumulator rows, zero between backward passes
+    size_t acc64_rows = 0;
+    std::vector<unsigned long long*> acc64_retired;   // outgrown rows: a captured graph may still point at them, freed with the context
     std::atomic<int*> overflow{nullptr};  // device flag raised by a capacity overflow (library- or caller-owned)
     int* overflow_owned = nullptr;
     std::mutex mu;                    // lazy allocations
@@ -316,6 +363,392 @@ int check_common(int P, int W, int H, const void* means3D)
     return 0;
 }
 
+// The options as ONE forward or backward sees them: read once at entry, so that a dgs_set_option from another thread affects this
+// call as a whole or the next one (a stage that sized a buffer by one value and launched by another would write past it).
+struct Options {
+    int v[DGS_OPT_COUNT];
+    int* overflow;
+    int operator[](int key) const { return v[key]; }
+};
+
+Options read_options(dgs_context* ctx, const ImageLayout& il)
+{
+    Options o;
+    for (int k = 0; k < DGS_OPT_COUNT; k++) o.v[k] = ctx->opt[k].load();
+    o.overflow = ctx->overflow.load();
+    if (o.v[DGS_OPT_TILE_ORDER] == 4 && dgs::order_groups(il.tiles_x, il.tiles_y) > dgs::kOrderMaxGroups) o.v[DGS_OPT_TILE_ORDER] = 3;   // > 128 x 128 tiles
+    if (o.v[DGS_OPT_CAPACITY] == 0) o.v[DGS_OPT_LIST_HINT] = 0;   // the promise belongs to capacity mode
+    return o;
+}
+
+// What the stages of one forward or one backward share.  A stage returns 0 or a negative status (stage_done).
+struct Pass {
+    dgs_context* ctx; hipStream_t stream; int debug;
+    const Options& opt;
+    int P; const int* radii;
+    const GeomLayout& gl; const ImageLayout& il;
+    const GeomView g; const ImageView im;
+    BinningView b;           // forward: from the scatter on
+    int R;                   // forward: from the read of num_rendered on
+    bool merged_offsets;     // tile counts -> ranges, cursors and order in one launch
+    bool order_later;        // ... but tile_last and the order by the scatter launch's rider workgroup
+    dgs::BinArgs bin;        // of the count launch, completed for the scatter launch
+    uint32_t longest;        // longest tile list, as far as the host knows it
+    bool need_global_sort;   // a list may exceed the LDS sorts: the binning buffer has the global-memory scratch
+    bool prep_fused;         // accumulator clear and tile order in one launch (prep_bwd_kernel)
+};
+
+// ---- forward stages -----------------------------------------------------------------------------------------------------------------
+// K2 preprocess
+int preprocess_fwd(const Pass& c, int D, int M, const float* means3D, const float* scales, const float* rotations, const float* opacities,
+                   const float* shs, const float* colors_precomp, const dgs::Camera& cam, int* radii)
+{
+    dgs::PreprocessArgs pa;
+    pa.P = c.P; pa.D = D; pa.M = M;
+    pa.means3D = means3D; pa.scales = scales; pa.rotations = rotations; pa.opacities = opacities;
+    pa.shs = shs; pa.colors_precomp = colors_precomp; pa.cam = cam;
+    pa.radii = radii;
+    pa.rec = c.g.rec;
+    pa.rects = c.g.rects;
+    pa.tight = c.opt[DGS_OPT_TIGHT_RECTS] ? 1 : 0;
+    pa.row_inv = 0;
+    size_t sh_lds = 0;
+    if (!colors_precomp && shs) {
+        if (M * 3 > 48 || M <= 0) return fail(DGS_ERR_INVALID_ARGUMENT, "forward: 1..16 SH coefficients per channel expected");
+        pa.row_inv = (unsigned)(0xFFFFFFFFu / (unsigned)(M * 3)) + 1u;
+        sh_lds = (size_t)dgs::kSurfelBlock * (M * 3 + 1) * sizeof(float);
+    }
+    Prof::Pair pp;
+    const bool timed = prof_begin(c.ctx, 2, c.stream, pp);
+    hipLaunchKernelGGL(dgs::preprocess_fwd_kernel, dim3(c.gl.nblocks), dim3(dgs::kSurfelBlock), sh_lds, c.stream, pa);
+    if (timed) prof_mark_end(c.ctx, c.stream, pp);
+    return stage_done("preprocess_fwd", c.debug, c.stream);
+}
+
+// K3 per-tile entry counts
+int count_tiles(Pass& c)
+{
+    dgs::BinArgs& a = c.bin;
+    a.P = c.P; a.ntiles = c.il.ntiles; a.tiles_x = c.il.tiles_x; a.chunk = (c.P + dgs::kBinGroups - 1) / dgs::kBinGroups;
+    a.radii = c.radii; a.rects = c.g.rects; a.rec = c.g.rec; a.M = c.im.cursor; a.keys = nullptr;
+    a.state = c.g.state;
+    c.merged_offsets = c.il.lds_bins && c.opt[DGS_OPT_MERGED_OFFSETS];
+    a.sync = c.merged_offsets ? c.im.tile_counts : nullptr;
+    a.nsync = 2 * c.il.off_blocks + 1;
+    a.ranges = nullptr; a.order = nullptr; a.group_xcd = nullptr; a.tile_last = nullptr; a.tiles_y = c.il.tiles_y; a.order_mode = 0;
+    if (c.il.lds_bins) {
+        hipLaunchKernelGGL(dgs::count_tiles_lds_kernel, dim3(dgs::kBinGroups), dim3(dgs::kBinThreads), c.il.hist_bytes, c.stream, a);
+        if (!c.merged_offsets)
+            hipLaunchKernelGGL(dgs::column_pass_kernel, dim3(c.il.off_blocks), dim3(64 * dgs::kColGroups), 0, c.stream, c.im.cursor, c.il.ntiles,
+                               (const uint2*)nullptr, c.im.tile_counts);
+    } else {
+        DGS_HIP(hipMemsetAsync(c.im.tile_counts, 0, c.il.hist_bytes, c.stream));
+        hipLaunchKernelGGL(dgs::count_tiles_global_kernel, dim3(c.gl.nblocks), dim3(dgs::kSurfelBlock), 0, c.stream, c.P, c.radii,
+                           (const uint2*)c.g.rects, c.il.tiles_x, c.im.tile_counts);
+    }
+    return stage_done("count_tiles", c.debug, c.stream);
+}
+
+// K3/K6 scan of the T tile counts -> tile ranges, num_rendered, longest list (+ the forward's dispatch order)
+int scan_tiles(Pass& c)
+{
+    const int capacity = c.opt[DGS_OPT_CAPACITY], tile_order = c.opt[DGS_OPT_TILE_ORDER];
+    uint32_t* order = tile_order >= 3 ? c.im.order_fwd : nullptr;
+    c.order_later = false;
+    if (c.merged_offsets) {
+        // column sums + scan + bucket cursors + dispatch order in one launch (binning_kernels.h: bin_offsets_kernel)
+        dgs::OffsetsArgs oa;
+        oa.M = c.im.cursor; oa.ntiles = c.il.ntiles; oa.ranges = c.im.ranges; oa.state = c.g.state;
+        oa.cap = (uint32_t)capacity; oa.overflow = c.opt.overflow; oa.list_hint = (uint32_t)c.opt[DGS_OPT_LIST_HINT];
+        oa.order = order;
+        oa.tiles_x = c.il.tiles_x; oa.tiles_y = c.il.tiles_y; oa.order_mode = tile_order;
+        oa.group_xcd = c.im.group_xcd; oa.tile_last = c.im.tile_last;
+        oa.long_thr = &c.im.long_thr->fwd; oa.long_div = (uint32_t)c.opt[DGS_OPT_LONG_DIV_FWD];
+        oa.sync = c.im.tile_counts;
+        // capacity mode: the scatter launch always follows (R = capacity > 0) and carries the order as a rider workgroup
+        oa.order_later = (capacity > 0 && order != nullptr && c.opt[DGS_OPT_ORDER_RIDER]) ? 1 : 0;
+        c.order_later = oa.order_later != 0;
+        hipLaunchKernelGGL(dgs::bin_offsets_kernel, dim3(c.il.off_blocks), dim3(64 * dgs::kColGroups), 0, c.stream, oa);
+    } else
+        hipLaunchKernelGGL(dgs::scan_tiles_kernel, dim3(1), dim3(1024), 0, c.stream, (const uint32_t*)c.im.tile_counts, c.il.ntiles, c.im.ranges,
+                           c.il.lds_bins ? (uint32_t*)nullptr : c.im.cursor, c.g.state, (uint32_t)capacity, c.opt.overflow, order,
+                           (uint32_t)c.opt[DGS_OPT_LIST_HINT], c.il.tiles_x, c.il.tiles_y, tile_order, c.im.group_xcd, c.im.tile_last,
+                           &c.im.long_thr->fwd, (uint32_t)c.opt[DGS_OPT_LONG_DIV_FWD]);
+    return stage_done("scan_tiles", c.debug, c.stream);
+}
+
+// num_rendered to the host: the binning buffer is sized from it (rasterizer_impl.cu:281-285).  Capacity mode skips the round trip: the
+// buffer is sized for the capacity, every sort variant is launched (each tile picks its own), and the value returned to the caller is
+// the capacity.
+int read_num_rendered(Pass& c)
+{
+    uint32_t R_u = 0;
+    if (c.opt[DGS_OPT_CAPACITY] > 0) {
+        R_u = (uint32_t)c.opt[DGS_OPT_CAPACITY];
+        const int hint = c.opt[DGS_OPT_LIST_HINT];
+        c.longest = hint > 0 ? (uint32_t)hint : 0xffffffffu;   // a longer list than promised raises the overflow flag (scan_tiles_kernel)
+    } else {
+        // one pinned word per context: concurrent forwards of the same context take turns here (other contexts do not wait)
+        HostStage& stage = c.ctx->stage;
+        std::lock_guard<std::mutex> lk(stage.mu);
+        if (stage.ensure()) return fail(DGS_ERR_HIP, "hipHostMalloc failed");
+        DGS_HIP(hipMemcpyAsync(stage.u, c.g.state, 8, hipMemcpyDeviceToHost, c.stream));
+        DGS_HIP(hipStreamSynchronize(c.stream));
+        R_u = stage.u[0];
+        c.longest = stage.u[1];
+    }
+    if (R_u > 0x7fffffffu) return fail(DGS_ERR_INVALID_ARGUMENT, "num_rendered overflows int32");
+    c.R = (int)R_u;
+    c.need_global_sort = c.longest > (c.opt[DGS_OPT_TILE_SORT] == 2 ? (uint32_t)dgs::kSegCap : 16384u);   // (radix mode: scratch for the sorted segments)
+    return 0;
+}
+
+// K4 scatter (depth, index) keys into the tile buckets
+int scatter_keys(Pass& c)
+{
+    if (c.il.lds_bins) {
+        if (!c.merged_offsets)
+            hipLaunchKernelGGL(dgs::column_pass_kernel, dim3(c.il.off_blocks), dim3(64 * dgs::kColGroups), 0, c.stream, c.im.cursor, c.il.ntiles,
+                               (const uint2*)c.im.ranges, (uint32_t*)nullptr);
+        dgs::BinArgs& a = c.bin;
+        a.keys = c.b.keys;
+        if (c.order_later) {
+            a.ranges = c.im.ranges; a.order = c.im.order_fwd; a.group_xcd = c.im.group_xcd;
+            a.tile_last = c.im.tile_last; a.order_mode = c.opt[DGS_OPT_TILE_ORDER];
+        }
+        const size_t scatter_lds = c.order_later && c.il.hist_bytes < dgs::kScatterRiderLds ? dgs::kScatterRiderLds : c.il.hist_bytes;
+        hipLaunchKernelGGL(dgs::scatter_keys_lds_kernel, dim3(dgs::kBinGroups + (c.order_later ? 1 : 0)), dim3(dgs::kBinThreads), scatter_lds, c.stream, a);
+    } else {
+        dgs::ScatterArgs sa;
+        sa.P = c.P; sa.radii = c.radii; sa.rec = c.g.rec; sa.rects = c.g.rects; sa.cursor = c.im.cursor;
+        sa.state = c.g.state;
+        sa.keys = c.b.keys;
+        sa.tiles_x = c.il.tiles_x;
+        hipLaunchKernelGGL(dgs::scatter_keys_kernel, dim3(c.gl.nblocks), dim3(dgs::kSurfelBlock), 0, c.stream, sa);
+    }
+    return stage_done("scatter_keys", c.debug, c.stream);
+}
+
+// K5 per-tile sort (stable radix order of rasterizer_impl.cu:304-309 = (tile, depth bits, surfel index))
+int sort_tiles(const Pass& c)
+{
+    const int ntiles = c.il.ntiles;
+    const uint2* ranges = c.im.ranges;
+    const uint64_t* keys = c.b.keys;
+    uint32_t* plist = c.b.point_list;
+    const bool capacity_mode = c.opt[DGS_OPT_CAPACITY] > 0;
+    const int big_grid = ntiles < 256 ? ntiles : 256;
+    if (c.opt[DGS_OPT_TILE_SORT] == 2) {
+        // per-tile LSD radix sort (default): lists up to 2048 entries in 36 KB of LDS (one workgroup per tile); longer ones as
+        // segments of 2048 sorted side by side by the same kernel + a rank / merge step, up to 28 segments; beyond 57 344 entries
+        // the global-memory network.  Every tile picks its kernel on the device; when the longest list is known on the host
+        // (exact-size mode, or promised) the launches that cannot have work are skipped.
+        hipLaunchKernelGGL((dgs::sort_tiles_radix_kernel<2048>), dim3(ntiles), dim3(256), 0, c.stream, ranges, ntiles, keys, plist, 0);
+        if (c.longest > (uint32_t)dgs::kSegCap) {
+            // (a 30 000-entry list on ONE workgroup's global-memory network took 0.45 ms; a crowded tile is exactly what
+            // densification produces)
+            // 256 columns of workgroups walk the tiles (64 were enough while segments were rare: at 1 M surfels / 1600 x 1600 thousands of
+            // tiles hold 2-4 k entries and a column handled 156 of them one after the other); rows that no list reaches exit at once
+            const dim3 seg_grid(big_grid, dgs::kMaxSegs);
+            const uint32_t* state = c.g.state;
+            hipLaunchKernelGGL((dgs::sort_tiles_radix_kernel<dgs::kSegCap, true>), seg_grid, dim3(256), 0, c.stream, ranges, ntiles, keys, plist, 0,
+                               c.b.scratch, state);
+            hipLaunchKernelGGL(dgs::merge_segments_kernel, seg_grid, dim3(256), 0, c.stream, ranges, ntiles, (const uint64_t*)c.b.scratch, plist, state);
+        }
+        if (c.longest > (uint32_t)(dgs::kSegCap * dgs::kMaxSegs))
+            hipLaunchKernelGGL(dgs::sort_tiles_global_kernel, dim3(big_grid), dim3(256), 0, c.stream, ranges, ntiles, keys, c.b.scratch, plist,
+                               dgs::kSegCap * dgs::kMaxSegs);
+    } else {
+        if (c.opt[DGS_OPT_TILE_SORT] == 1)
+            hipLaunchKernelGGL(dgs::sort_tiles_reg_kernel, dim3(ntiles), dim3(256), 0, c.stream, ranges, keys, plist);
+        else
+            hipLaunchKernelGGL((dgs::sort_tiles_lds_kernel<2048>), dim3(ntiles), dim3(256), 0, c.stream, ranges, keys, plist, 0);
+        // capacity mode does not know the longest list on the host: ONE fallback launch (global scratch) covers every tile
+        // above 2048 entries instead of two mostly empty ones
+        if (c.longest > 2048u && !capacity_mode)
+            hipLaunchKernelGGL((dgs::sort_tiles_lds_kernel<16384>), dim3(ntiles), dim3(256), 0, c.stream, ranges, keys, plist, 2048);
+        if (c.need_global_sort)
+            hipLaunchKernelGGL(dgs::sort_tiles_global_kernel, dim3(big_grid), dim3(256), 0, c.stream, ranges, ntiles, keys, c.b.scratch, plist,
+                               capacity_mode ? 2048 : 16384);
+    }
+    return stage_done("sort_tiles", c.debug, c.stream);
+}
+
+// K7 forward blend
+int blend_fwd(const Pass& c, int width, int height, const float* background, float* out_color, float* out_others)
+{
+    const int tile_order = c.opt[DGS_OPT_TILE_ORDER], grid_limit = c.opt[DGS_OPT_GRID_LIMIT_FWD];
+    dgs::BlendFwdArgs fa;
+    fa.ranges = c.im.ranges;
+    fa.point_list = c.b.point_list;
+    fa.rec = c.g.rec;
+    fa.W = width; fa.H = height; fa.tiles_x = c.il.tiles_x; fa.tiles_y = c.il.tiles_y; fa.mode = tile_order;
+    fa.order = c.im.order_fwd;   // written by scan_tiles_kernel
+    fa.bg = background;
+    fa.final_T = c.im.final_T;
+    fa.n_contrib = c.im.n_contrib;
+    fa.tile_last = c.im.tile_last;
+    fa.out_color = out_color;
+    fa.out_others = out_others;
+    int grid = dgs::blend_grid_size(c.il.tiles_x, c.il.tiles_y, tile_order);
+    fa.long_thr = nullptr;
+    if (tile_order == 3 && c.opt[DGS_OPT_LONG_TILES] && !grid_limit) {   // long-tile path (blend_common.h): four workgroups for the longest lists
+        fa.long_thr = c.im.long_thr;
+        grid = dgs::long_grid_size(c.il.ntiles);
+    }
+    if (grid_limit) {
+        grid = grid_limit < grid ? grid_limit : grid;
+        DGS_HIP(hipMemsetAsync(c.im.final_T, 0, c.il.ranges - c.il.final_T, c.stream));   // final_T, n_contrib of the skipped tiles
+        DGS_HIP(hipMemsetAsync(c.im.tile_last, 0, (size_t)c.il.ntiles * 4, c.stream));
+    }
+    // accumulator rider: 256 workgroups in FRONT of the tile workgroups (they hold a slot for a few microseconds each while the tile
+    // workgroups fill the rest of the chip; at the end of the grid they would lengthen the drain)
+    fa.clear = nullptr; fa.clear_n4 = 0; fa.clear_blocks = 0;
+    fa.clean_flag = c.g.state + 3;
+    const size_t acc_bytes = (size_t)c.P * dgs::kAccFloats * 4;
+    if (c.opt[DGS_OPT_ACC_RIDER] && !grid_limit && tile_order >= 3 && acc_bytes % 16 == 0 && acc_bytes / 16 < 0xf0000000ull) {
+        fa.clear = (float4*)c.g.acc;
+        fa.clear_n4 = (uint32_t)(acc_bytes / 16);
+        fa.clear_blocks = (int)std::min<size_t>(256, ((fa.clear_n4 + 16 * dgs::kTilePix - 1) / (16 * dgs::kTilePix) + 7) / 8 * 8);   // ~16 stores per thread
+        grid += fa.clear_blocks;
+    }
+    Prof::Pair pp;
+    const bool timed = prof_begin(c.ctx, 0, c.stream, pp);
+    hipLaunchKernelGGL(dgs::blend_fwd_rows_kernel, dim3(grid), dim3(dgs::kTilePix), 0, c.stream, fa);
+    if (timed) prof_end(c.ctx, c.stream, pp, fa.tile_last, c.il.ntiles);
+    return stage_done("blend_fwd", c.debug, c.stream);
+}
+
+// ---- backward stages ----------------------------------------------------------------------------------------------------------------
+// accumulator rows cleared and (tile orders 3, 4) the tiles ordered by the traversed length the forward measured: one launch
+int prep_bwd(Pass& c)
+{
+    const int mode = c.opt[DGS_OPT_TILE_ORDER];
+    const size_t acc_bytes = (size_t)c.P * dgs::kAccFloats * 4;
+    c.prep_fused = c.R > 0 && mode >= 3 && acc_bytes % 16 == 0 && (reinterpret_cast<size_t>(c.g.acc) & 15) == 0;
+    if (c.prep_fused) {
+        const size_t n4 = acc_bytes / 16;
+        const int fill_blocks = (int)std::min<size_t>(1024, (n4 + 4 * 1024 - 1) / (4 * 1024));   // ~4 stores of 16 B per thread
+        hipLaunchKernelGGL(dgs::prep_bwd_kernel, dim3(fill_blocks + 1), dim3(1024), 0, c.stream, (float4*)c.g.acc, n4,
+                           (const uint32_t*)c.im.tile_last, c.il.tiles_x, c.il.tiles_y, mode, c.im.order_bwd, c.im.group_xcd, &c.im.long_thr->fwd,
+                           (uint32_t)c.opt[DGS_OPT_LONG_DIV_BWD],
+                           (const uint32_t*)c.g.state + 3);   // (the forward rider's flag; blend_bwd_kernel resets it)
+        return stage_done("prep_bwd", c.debug, c.stream);
+    }
+    DGS_HIP(hipMemsetAsync(c.g.acc, 0, acc_bytes, c.stream));
+    if (c.R > 0 && mode >= 3) {  // by the traversed length the forward measured
+        hipLaunchKernelGGL(dgs::tile_order_kernel, dim3(1), dim3(1024), 0, c.stream, (const uint2*)nullptr, (const uint32_t*)c.im.tile_last,
+                           c.il.tiles_x, c.il.tiles_y, mode, c.im.order_bwd, c.im.group_xcd);
+        return stage_done("tile_order_bwd", c.debug, c.stream);
+    }
+    return 0;
+}
+
+// K8 backward blend, by determinism mode
+int blend_bwd(const Pass& c, int width, int height, const float* background, const float* dL_dpix, const float* dL_dothers)
+{
+    dgs_context* ctx = c.ctx;
+    const int P = c.P, grid_limit = c.opt[DGS_OPT_GRID_LIMIT_BWD];
+    dgs::BlendBwdArgs a;
+    a.ranges = c.im.ranges;
+    a.point_list = c.b.point_list;
+    a.rec = c.g.rec;
+    a.W = width; a.H = height; a.tiles_x = c.il.tiles_x; a.tiles_y = c.il.tiles_y; a.mode = c.opt[DGS_OPT_TILE_ORDER];
+    a.order = c.im.order_bwd;
+    a.bg = background;
+    a.final_T = c.im.final_T;
+    a.n_contrib = c.im.n_contrib;
+    a.tile_last = c.im.tile_last;
+    a.dL_dpix = dL_dpix;
+    a.dL_dothers = dL_dothers;
+    a.acc = c.g.acc;
+    a.clean_flag = c.g.state + 3;
+    int grid = dgs::blend_grid_size(c.il.tiles_x, c.il.tiles_y, a.mode);
+    a.long_thr = nullptr;
+    if (a.mode == 3 && c.prep_fused && c.opt[DGS_OPT_LONG_TILES] && !grid_limit) {   // long-tile path (blend_common.h)
+        a.long_thr = c.im.long_thr;
+        grid = dgs::long_grid_size(c.il.ntiles);
+    }
+    if (grid_limit) grid = grid_limit < grid ? grid_limit : grid;
+    Prof::Pair pp;
+    const bool timed = prof_begin(ctx, 1, c.stream, pp);
+    if (c.opt[DGS_OPT_DETERMINISTIC] == 2) {
+        // fixed-point sums with integer atomics: order-free, capturable.  The rows live in the context (zero between backward
+        // passes: fixed_to_acc_kernel clears what it converts); they are (re)allocated outside a capture only
+        {
+            std::lock_guard<std::mutex> lk(ctx->mu);
+            if (ctx->acc64_rows < (size_t)P) {
+                hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+                (void)hipStreamIsCapturing(c.stream, &cs);
+                if (cs != hipStreamCaptureStatusNone)
+                    return fail(DGS_ERR_INVALID_ARGUMENT, "deterministic backward (option 7 = 2): the fixed-point rows must exist before a capture (run one eager backward at this size first)");
+                DGS_HIP(hipStreamSynchronize(c.stream));
+                // the outgrown rows are RETIRED, not freed: a graph captured at the smaller size has their address baked
+                // in and may still be replayed (its sums then land in rows nobody converts -- a stale graph, but not a write into
+                // freed memory).  Two backward passes on different streams of ONE context would still share the live rows: callers
+                // that run views concurrently give each its own context (diff_surfel_rasterization.Lane).
+                if (ctx->acc64) ctx->acc64_retired.push_back(ctx->acc64);
+                ctx->acc64 = nullptr; ctx->acc64_rows = 0;
+                const size_t rows = (size_t)P + (size_t)P / 4 + 1024;
+                DGS_HIP(hipMalloc((void**)&ctx->acc64, rows * dgs::kAccFloats * sizeof(unsigned long long)));
+                DGS_HIP(hipMemset(ctx->acc64, 0, rows * dgs::kAccFloats * sizeof(unsigned long long)));
+                ctx->acc64_rows = rows;
+            }
+        }
+        a.det_part = nullptr;
+        a.acc64 = ctx->acc64;
+        hipLaunchKernelGGL(dgs::blend_bwd_kernel<2>, dim3(grid), dim3(dgs::kTilePix), 0, c.stream, a);
+        const size_t n = (size_t)P * dgs::kAccFloats;
+        hipLaunchKernelGGL(dgs::fixed_to_acc_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c.stream, ctx->acc64, c.g.acc, n);
+    } else if (c.opt[DGS_OPT_DETERMINISTIC] == 1) {
+        // test option: every (list entry, wave) stores its sums in a row of its own, a per-surfel kernel adds them in a fixed
+        // order.  R x 320 bytes of scratch from the stream-ordered allocator (not capturable: tests run eagerly)
+        float* part = nullptr;
+        const size_t bytes = (size_t)c.R * dgs::kDetRows * dgs::kAccFloats * sizeof(float);
+        DGS_HIP(hipMallocAsync((void**)&part, bytes, c.stream));
+        DGS_HIP(hipMemsetAsync(part, 0, bytes, c.stream));
+        a.det_part = part;
+        hipLaunchKernelGGL(dgs::blend_bwd_kernel<1>, dim3(grid), dim3(dgs::kTilePix), 0, c.stream, a);
+        hipLaunchKernelGGL(dgs::det_reduce_kernel, dim3((P + 255) / 256), dim3(256), 0, c.stream, P, c.radii, (const uint2*)c.g.rects, c.il.tiles_x,
+                           a.ranges, a.point_list, (const float*)part, c.g.acc);
+        DGS_HIP(hipFreeAsync(part, c.stream));
+    } else {
+        a.det_part = nullptr;
+        a.acc64 = nullptr;
+        hipLaunchKernelGGL(dgs::blend_bwd_kernel<0>, dim3(grid), dim3(dgs::kTilePix), 0, c.stream, a);
+    }
+    if (timed) prof_end(ctx, c.stream, pp, a.tile_last, c.il.ntiles);
+    return stage_done("blend_bwd", c.debug, c.stream);
+}
+
+// K9 + K10 fused per-surfel backward
+int surfel_bwd(const Pass& c, int D, int M, const float* means3D, const float* scales, const float* rotations, const float* shs,
+               const dgs::Camera& cam, float* dL_dmean2D, float* dL_dnormal, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
+               float* dL_dtransMat, float* dL_dsh, float* dL_dscale, float* dL_drot)
+{
+    dgs::SurfelBwdArgs sa;
+    sa.P = c.P; sa.D = D; sa.M = M;
+    sa.means3D = means3D; sa.scales = scales; sa.rotations = rotations;
+    sa.shs = shs;
+    sa.cam = cam;
+    sa.radii = c.radii;
+    sa.rec = c.g.rec;
+    sa.acc = c.g.acc;
+    sa.dL_dmean2D = dL_dmean2D; sa.dL_dnormal = dL_dnormal; sa.dL_dopacity = dL_dopacity; sa.dL_dcolor = dL_dcolor;
+    sa.dL_dmean3D = dL_dmean3D; sa.dL_dtransMat = dL_dtransMat; sa.dL_dsh = dL_dsh; sa.sh_all_rows = c.opt[DGS_OPT_SH_ALL_ROWS]; sa.dL_dscale = dL_dscale; sa.dL_drot = dL_drot;
+    size_t sh_lds = 0;
+    if (sa.shs) {
+        if (M * 3 > 48) return fail(DGS_ERR_INVALID_ARGUMENT, "backward: more than 16 SH coefficients per channel");
+        sa.row_inv = (unsigned)(0xFFFFFFFFu / (unsigned)(M * 3)) + 1u;
+        sh_lds = (size_t)dgs::kSurfelBlock * (M * 3 + 1) * sizeof(float);
+    }
+    Prof::Pair pp;
+    const bool timed = prof_begin(c.ctx, 4, c.stream, pp);
+    hipLaunchKernelGGL(dgs::surfel_bwd_kernel, dim3(c.gl.nblocks), dim3(dgs::kSurfelBlock), sh_lds, c.stream, sa);
+    if (timed) prof_mark_end(c.ctx, c.stream, pp);
+    return stage_done("surfel_bwd", c.debug, c.stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -356,51 +789,22 @@ void dgs_context_destroy(dgs_context* c)
 int dgs_context_set_option(dgs_context* c, int key, int value)
 {
     if (!c) return fail(DGS_ERR_INVALID_ARGUMENT, "context is NULL");
-    if (key == 0) { c->tight_rects.store(value != 0); return DGS_OK; }
-    if (key == 1 && value >= 0 && value <= 4) { c->tile_order.store(value); return DGS_OK; }
-    if (key == 7 && value >= 0 && value <= 2) { c->deterministic.store(value); return DGS_OK; }
-    if (key == 8) { c->sh_all_rows.store(value != 0); return DGS_OK; }
-    if (key == 9) { c->long_tiles.store(value != 0); return DGS_OK; }
-    if (key == 10 && value > 0) { c->long_div_fwd.store(value); return DGS_OK; }
-    if (key == 11 && value > 0) { c->long_div_bwd.store(value); return DGS_OK; }
-    if (key == 12) { c->merged_offsets.store(value != 0); return DGS_OK; }
-    if (key == 13) { c->order_rider.store(value != 0); return DGS_OK; }
-    if (key == 14) { c->acc_rider.store(value != 0); return DGS_OK; }
-    if (key == 3 && value >= 0 && value <= 2) { c->sort_regs.store(value); return DGS_OK; }
-    if (key == 4 && value >= 0) { c->grid_limit_bwd.store(value); return DGS_OK; }
-    if (key == 6 && value >= 0) { c->list_hint.store(value); return DGS_OK; }
-    if (key == 5 && value >= 0) { c->grid_limit_fwd.store(value); return DGS_OK; }
-    if (key == 2 && value >= 0) {
-        if (value > 0)
-            if (int e = ensure_overflow(c)) return e;
-        c->capacity.store(value);
-        if (value == 0) c->list_hint.store(0);   // the promise belongs to a capacity-mode session
-        return DGS_OK;
-    }
-    return fail(DGS_ERR_INVALID_ARGUMENT, "dgs_set_option: unknown key / value");
+    if (key < 0 || key >= DGS_OPT_COUNT) return fail(DGS_ERR_INVALID_ARGUMENT, "dgs_set_option: unknown key / value");
+    const OptionSpec& o = kOptions[key];
+    if (o.boolean) value = value != 0;
+    if (value < o.lo || value > o.hi) return fail(DGS_ERR_INVALID_ARGUMENT, "dgs_set_option: unknown key / value");
+    if (key == DGS_OPT_CAPACITY && value > 0)
+        if (int e = ensure_overflow(c)) return e;
+    c->opt[key].store(value);
+    if (key == DGS_OPT_CAPACITY && value == 0) c->opt[DGS_OPT_LIST_HINT].store(0);   // the promise belongs to a capacity-mode session
+    return DGS_OK;
 }
 
 int dgs_context_get_option(dgs_context* c, int key)
 {
     if (!c) return fail(DGS_ERR_INVALID_ARGUMENT, "context is NULL");
-    switch (key) {
-    case 0: return c->tight_rects.load();
-    case 1: return c->tile_order.load();
-    case 2: return c->capacity.load();
-    case 3: return c->sort_regs.load();
-    case 4: return c->grid_limit_bwd.load();
-    case 5: return c->grid_limit_fwd.load();
-    case 6: return c->list_hint.load();
-    case 7: return c->deterministic.load();
-    case 8: return c->sh_all_rows.load();
-    case 9: return c->long_tiles.load();
-    case 10: return c->long_div_fwd.load();
-    case 11: return c->long_div_bwd.load();
-    case 12: return c->merged_offsets.load();
-    case 13: return c->order_rider.load();
-    case 14: return c->acc_rider.load() ? 1 : 0;
-    }
-    return fail(DGS_ERR_INVALID_ARGUMENT, "dgs_get_option: unknown key");
+    if (key < 0 || key >= DGS_OPT_COUNT) return fail(DGS_ERR_INVALID_ARGUMENT, "dgs_get_option: unknown key");
+    return c->opt[key].load();
 }
 
 int dgs_context_set_overflow_flag(dgs_context* c, int* device_flag)
@@ -411,7 +815,7 @@ int dgs_context_set_overflow_flag(dgs_context* c, int* device_flag)
         return DGS_OK;
     }
     c->overflow.store(c->overflow_owned);   // back to the library-owned flag (allocated on demand)
-    if (!c->overflow_owned && c->capacity.load() > 0) return ensure_overflow(c);
+    if (!c->overflow_owned && c->opt[DGS_OPT_CAPACITY].load() > 0) return ensure_overflow(c);
     return DGS_OK;
 }
 
@@ -509,7 +913,7 @@ int dgs_context_profile_read(dgs_context* c, double* out, int cap)
 }
 
 // ---- the same knobs on the default context of the calling thread's current device --------------------------------------
-void dgs_set_tight_rects(int on) { (void)dgs_context_set_option(default_context(), 0, on); }
+void dgs_set_tight_rects(int on) { (void)dgs_context_set_option(default_context(), DGS_OPT_TIGHT_RECTS, on); }
 int dgs_set_option(int key, int value) { return dgs_context_set_option(default_context(), key, value); }
 int dgs_get_option(int key) { return dgs_context_get_option(default_context(), key); }
 int dgs_set_overflow_flag(int* device_flag) { return dgs_context_set_overflow_flag(default_context(), device_flag); }
@@ -528,7 +932,6 @@ int dgs_debug_layout(int which, int P, int width, int height, int R, size_t* off
         ImageLayout m(width, height);
         v = {m.final_T, m.n_contrib, m.ranges, m.tile_last, m.order_fwd, m.order_bwd, m.tile_counts, m.cursor, m.bytes};
     } else if (which == 2) {
-        ImageLayout m(width, height);
         BinningLayout b(R, false);
         v = {b.point_list, b.keys, b.scratch, b.bytes};
     } else {
@@ -548,8 +951,7 @@ int dgs_rasterizer_mark_visible(int P, const float* means3D, const float* viewma
     if (P == 0) return DGS_OK;
     if (!means3D || !viewmatrix || !present) return fail(DGS_ERR_INVALID_ARGUMENT, "NULL pointer");
     hipLaunchKernelGGL(dgs::mark_visible_kernel, dim3((P + 255) / 256), dim3(256), 0, stream, P, means3D, viewmatrix, present);
-    DGS_STAGE("mark_visible", 0, stream);
-    return DGS_OK;
+    return stage_done("mark_visible", 0, stream);
 }
 
 int dgs_context_forward(dgs_context* ctx, dgs_alloc_fn geometry_alloc, void* geometry_ctx, dgs_alloc_fn binning_alloc, void* binning_ctx,
@@ -575,236 +977,42 @@ int dgs_context_forward(dgs_context* ctx, dgs_alloc_fn geometry_alloc, void* geo
         return fail(DGS_ERR_INVALID_ARGUMENT, "SH degree / coefficient count mismatch");
     if (D < 0) D = 0;
 
-    GeomLayout gl(P);
-    ImageLayout il(width, height);
+    const GeomLayout gl(P);
+    const ImageLayout il(width, height);
     char* geom = geometry_alloc(geometry_ctx, gl.bytes);
     char* img = image_alloc(image_ctx, il.bytes);
     if (!geom || !img) return fail(DGS_ERR_ALLOC, "geometry/image allocator returned NULL");
-    if (!radii) radii = (int*)(geom + gl.internal_radii);  // rasterizer_impl.cu:230-233
+    const Options opt = read_options(ctx, il);
+    Pass c{ctx, stream, debug, opt, P, radii, gl, il, GeomView(gl, geom), ImageView(il, img)};
+    if (!radii) c.radii = radii = c.g.internal_radii;  // rasterizer_impl.cu:230-233
 
-    const dgs::Camera cam = make_camera(viewmatrix, cam_pos, width, height, tan_fovx, tan_fovy);
-
-    // ---- K2 preprocess
-    uint32_t* tile_counts = (uint32_t*)(img + il.tile_counts);
-    uint32_t* cursor = (uint32_t*)(img + il.cursor);
-    uint2* ranges = (uint2*)(img + il.ranges);
-    dgs::PreprocessArgs pa;
-    pa.P = P; pa.D = D; pa.M = M;
-    pa.means3D = means3D; pa.scales = scales; pa.rotations = rotations; pa.opacities = opacities;
-    pa.shs = shs; pa.colors_precomp = colors_precomp; pa.cam = cam;
-    pa.radii = radii;
-    pa.rec = (float4*)(geom + gl.rec);
-    pa.rects = (uint2*)(geom + gl.rects);
-    pa.tight = ctx->tight_rects.load() ? 1 : 0;
-    pa.row_inv = 0;
-    size_t sh_lds = 0;
-    if (!colors_precomp && shs) {
-        if (M * 3 > 48 || M <= 0) return fail(DGS_ERR_INVALID_ARGUMENT, "forward: 1..16 SH coefficients per channel expected");
-        pa.row_inv = (unsigned)(0xFFFFFFFFu / (unsigned)(M * 3)) + 1u;
-        sh_lds = (size_t)dgs::kSurfelBlock * (M * 3 + 1) * sizeof(float);
-    }
-    Prof::Pair pp2;
-    const bool timed2 = prof_begin(ctx, 2, stream, pp2);
-    hipLaunchKernelGGL(dgs::preprocess_fwd_kernel, dim3(gl.nblocks), dim3(dgs::kSurfelBlock), sh_lds, stream, pa);
-    if (timed2) prof_mark_end(ctx, stream, pp2);
-    DGS_STAGE("preprocess_fwd", debug, stream);
-    Prof::Pair pp3;
+    if (int e = preprocess_fwd(c, D, M, means3D, scales, rotations, opacities, shs, colors_precomp,
+                               make_camera(viewmatrix, cam_pos, width, height, tan_fovx, tan_fovy), radii))
+        return e;
     // binning: count, column pass, scan, column pass, scatter, sort.  (Exact-size mode: the span also contains the D2H copy of
     // num_rendered, the stream synchronisation and the caller's allocator below -- its time is kernel time only in capacity mode,
     // which is where bench.py reads it.)
-    const bool timed3 = prof_begin(ctx, 3, stream, pp3);
-    // ---- K3 per-tile entry counts
-    dgs::BinArgs ba_;
-    ba_.P = P; ba_.ntiles = il.ntiles; ba_.tiles_x = il.tiles_x; ba_.chunk = (P + dgs::kBinGroups - 1) / dgs::kBinGroups;
-    ba_.radii = radii; ba_.rects = pa.rects; ba_.rec = pa.rec; ba_.M = cursor; ba_.keys = nullptr;
-    ba_.state = (const uint32_t*)(geom + gl.total);
-    const size_t hist_bytes = (size_t)il.ntiles * 4;
-    const int off_blocks = (il.ntiles + 63) / 64;
-    const bool merged_offsets = il.lds_bins && ctx->merged_offsets.load();
-    ba_.sync = merged_offsets ? tile_counts : nullptr;
-    ba_.nsync = 2 * off_blocks + 1;
-    ba_.ranges = nullptr; ba_.order = nullptr; ba_.group_xcd = nullptr; ba_.tile_last = nullptr; ba_.tiles_y = il.tiles_y; ba_.order_mode = 0;
-    if (il.lds_bins) {
-        hipLaunchKernelGGL(dgs::count_tiles_lds_kernel, dim3(dgs::kBinGroups), dim3(dgs::kBinThreads), hist_bytes, stream, ba_);
-        if (!merged_offsets)
-            hipLaunchKernelGGL(dgs::column_pass_kernel, dim3(off_blocks), dim3(64 * dgs::kColGroups), 0, stream, cursor, il.ntiles,
-                               (const uint2*)nullptr, tile_counts);
-    } else {
-        DGS_HIP(hipMemsetAsync(tile_counts, 0, hist_bytes, stream));
-        hipLaunchKernelGGL(dgs::count_tiles_global_kernel, dim3(gl.nblocks), dim3(dgs::kSurfelBlock), 0, stream, P, (const int*)radii,
-                           (const uint2*)pa.rects, il.tiles_x, tile_counts);
-    }
-    DGS_STAGE("count_tiles", debug, stream);
-    const int capacity = ctx->capacity.load();
-    int* overflow = ctx->overflow.load();
-    // ---- K3/K6 scan of the T tile counts -> tile ranges, num_rendered, longest list
-    int tile_order = ctx->tile_order.load();
-    if (tile_order == 4 && dgs::order_groups(il.tiles_x, il.tiles_y) > dgs::kOrderMaxGroups) tile_order = 3;   // > 128 x 128 tiles
-    bool order_later = false;
-    if (merged_offsets) {
-        // column sums + scan + bucket cursors + dispatch order in one launch (kernels_preprocess.h: bin_offsets_kernel)
-        dgs::OffsetsArgs oa;
-        oa.M = cursor; oa.ntiles = il.ntiles; oa.ranges = ranges; oa.state = (uint32_t*)(geom + gl.total);
-        oa.cap = (uint32_t)capacity; oa.overflow = overflow; oa.list_hint = (uint32_t)(capacity > 0 ? ctx->list_hint.load() : 0);
-        oa.order = tile_order >= 3 ? (uint32_t*)(img + il.order_fwd) : (uint32_t*)nullptr;
-        oa.tiles_x = il.tiles_x; oa.tiles_y = il.tiles_y; oa.order_mode = tile_order;
-        oa.group_xcd = (uint32_t*)(img + il.group_xcd); oa.tile_last = (uint32_t*)(img + il.tile_last);
-        oa.long_thr = (uint32_t*)(img + il.long_thr); oa.long_div = (uint32_t)ctx->long_div_fwd.load();
-        oa.sync = tile_counts;
-        // capacity mode: the scatter launch always follows (R = capacity > 0) and carries the order as a rider workgroup
-        oa.order_later = (capacity > 0 && oa.order != nullptr && ctx->order_rider.load()) ? 1 : 0;
-        order_later = oa.order_later != 0;
-        hipLaunchKernelGGL(dgs::bin_offsets_kernel, dim3(off_blocks), dim3(64 * dgs::kColGroups), 0, stream, oa);
-    } else
-    hipLaunchKernelGGL(dgs::scan_tiles_kernel, dim3(1), dim3(1024), 0, stream, (const uint32_t*)tile_counts, il.ntiles, ranges,
-                       il.lds_bins ? (uint32_t*)nullptr : cursor, (uint32_t*)(geom + gl.total), (uint32_t)capacity, overflow,
-                       tile_order >= 3 ? (uint32_t*)(img + il.order_fwd) : (uint32_t*)nullptr,   // + the forward's dispatch order
-                       (uint32_t)(capacity > 0 ? ctx->list_hint.load() : 0), il.tiles_x, il.tiles_y, tile_order,
-                       (uint32_t*)(img + il.group_xcd), (uint32_t*)(img + il.tile_last), (uint32_t*)(img + il.long_thr), (uint32_t)ctx->long_div_fwd.load());
-    DGS_STAGE("scan_tiles", debug, stream);
-
-    // ---- num_rendered to the host: the binning buffer is sized from it (rasterizer_impl.cu:281-285).
-    // Capacity mode skips the round trip: the buffer is sized for g_capacity entries, every sort variant is
-    // launched (each tile picks its own), and the value returned to the caller is the capacity.
-    uint32_t R_u = 0, longest = 0;
-    const bool capacity_mode = capacity > 0;
-    if (capacity_mode) {
-        R_u = (uint32_t)capacity;
-        const int hint = ctx->list_hint.load();
-        longest = hint > 0 ? (uint32_t)hint : 0xffffffffu;   // a longer list than promised raises the overflow flag (scan_tiles_kernel)
-    } else {
-        // one pinned word per context: concurrent forwards of the same context take turns here (other contexts do not wait)
-        std::lock_guard<std::mutex> lk(ctx->stage.mu);
-        if (ctx->stage.ensure()) return fail(DGS_ERR_HIP, "hipHostMalloc failed");
-        DGS_HIP(hipMemcpyAsync(ctx->stage.u, geom + gl.total, 8, hipMemcpyDeviceToHost, stream));
-        DGS_HIP(hipStreamSynchronize(stream));
-        R_u = ctx->stage.u[0];
-        longest = ctx->stage.u[1];
-    }
-    if (R_u > 0x7fffffffu) return fail(DGS_ERR_INVALID_ARGUMENT, "num_rendered overflows int32");
-    const int R = (int)R_u;
-
-    const bool need_global_sort = longest > (ctx->sort_regs.load() == 2 ? (uint32_t)dgs::kSegCap : 16384u);   // (radix mode: scratch for the sorted segments)
-    BinningLayout bl(R, need_global_sort);
+    Prof::Pair pp;
+    const bool timed = prof_begin(ctx, 3, stream, pp);
+    if (int e = count_tiles(c)) return e;
+    if (int e = scan_tiles(c)) return e;
+    if (int e = read_num_rendered(c)) return e;
+    const BinningLayout bl(c.R, c.need_global_sort);
     char* bin = binning_alloc(binning_ctx, bl.bytes);
     if (!bin) return fail(DGS_ERR_ALLOC, "binning allocator returned NULL");
-    if (R > 0) {
-        // ---- K4 scatter (depth, index) keys into the tile buckets
-        uint64_t* keys = (uint64_t*)(bin + bl.keys);
-        if (il.lds_bins) {
-            if (!merged_offsets)
-                hipLaunchKernelGGL(dgs::column_pass_kernel, dim3(off_blocks), dim3(64 * dgs::kColGroups), 0, stream, cursor, il.ntiles,
-                                   (const uint2*)ranges, (uint32_t*)nullptr);
-            ba_.keys = keys;
-            if (order_later) {
-                ba_.ranges = ranges; ba_.order = (uint32_t*)(img + il.order_fwd); ba_.group_xcd = (uint32_t*)(img + il.group_xcd);
-                ba_.tile_last = (uint32_t*)(img + il.tile_last); ba_.order_mode = tile_order;
-            }
-            const size_t scatter_lds = order_later && hist_bytes < dgs::kScatterRiderLds ? dgs::kScatterRiderLds : hist_bytes;
-            hipLaunchKernelGGL(dgs::scatter_keys_lds_kernel, dim3(dgs::kBinGroups + (order_later ? 1 : 0)), dim3(dgs::kBinThreads), scatter_lds, stream, ba_);
-        } else {
-            dgs::ScatterArgs sa;
-            sa.P = P; sa.radii = radii; sa.rec = pa.rec; sa.rects = pa.rects; sa.cursor = cursor;
-            sa.state = (const uint32_t*)(geom + gl.total);
-            sa.keys = keys;
-            sa.tiles_x = il.tiles_x;
-            hipLaunchKernelGGL(dgs::scatter_keys_kernel, dim3(gl.nblocks), dim3(dgs::kSurfelBlock), 0, stream, sa);
-        }
-        DGS_STAGE("scatter_keys", debug, stream);
-        // ---- K5 per-tile sort (stable radix order of rasterizer_impl.cu:304-309 = (tile, depth bits, surfel index))
-        uint32_t* plist = (uint32_t*)(bin + bl.point_list);
-        const int sort_mode = ctx->sort_regs.load();
-        if (sort_mode == 2) {
-            // per-tile LSD radix sort (default): lists up to 2048 entries in 36 KB of LDS (one workgroup per tile); longer ones as
-            // segments of 2048 sorted side by side by the same kernel + a rank / merge step, up to 28 segments; beyond 57 344 entries
-            // the global-memory network.  Every tile picks its kernel on the device; when the longest list is known on the host
-            // (exact-size mode, or promised) the launches that cannot have work are skipped.
-            const int big_grid = il.ntiles < 256 ? il.ntiles : 256;
-            hipLaunchKernelGGL((dgs::sort_tiles_radix_kernel<2048>), dim3(il.ntiles), dim3(256), 0, stream, (const uint2*)ranges, il.ntiles,
-                               (const uint64_t*)keys, plist, 0);
-            if (longest > (uint32_t)dgs::kSegCap) {
-                // (a 30 000-entry list on ONE workgroup's global-memory network took 0.45 ms; a crowded tile is exactly what
-                // densification produces)
-                // 256 columns of workgroups walk the tiles (64 were enough while segments were rare: at 1 M surfels / 1600 x 1600 thousands of
-                // tiles hold 2-4 k entries and a column handled 156 of them one after the other); rows that no list reaches exit at once
-                const dim3 seg_grid(il.ntiles < 256 ? il.ntiles : 256, dgs::kMaxSegs);
-                const uint32_t* state = (const uint32_t*)(geom + gl.total);
-                hipLaunchKernelGGL((dgs::sort_tiles_radix_kernel<dgs::kSegCap, true>), seg_grid, dim3(256), 0, stream, (const uint2*)ranges, il.ntiles,
-                                   (const uint64_t*)keys, plist, 0, (uint64_t*)(bin + bl.scratch), state);
-                hipLaunchKernelGGL(dgs::merge_segments_kernel, seg_grid, dim3(256), 0, stream, (const uint2*)ranges, il.ntiles,
-                                   (const uint64_t*)(bin + bl.scratch), plist, state);
-            }
-            if (longest > (uint32_t)(dgs::kSegCap * dgs::kMaxSegs))
-                hipLaunchKernelGGL(dgs::sort_tiles_global_kernel, dim3(big_grid), dim3(256), 0, stream, (const uint2*)ranges, il.ntiles,
-                                   (const uint64_t*)keys, (uint64_t*)(bin + bl.scratch), plist, dgs::kSegCap * dgs::kMaxSegs);
-        } else {
-            if (sort_mode == 1)
-                hipLaunchKernelGGL(dgs::sort_tiles_reg_kernel, dim3(il.ntiles), dim3(256), 0, stream, (const uint2*)ranges,
-                                   (const uint64_t*)keys, plist);
-            else
-                hipLaunchKernelGGL((dgs::sort_tiles_lds_kernel<2048>), dim3(il.ntiles), dim3(256), 0, stream, (const uint2*)ranges,
-                                   (const uint64_t*)keys, plist, 0);
-            // capacity mode does not know the longest list on the host: ONE fallback launch (global scratch) covers every tile
-            // above 2048 entries instead of two mostly empty ones
-            if (longest > 2048u && !capacity_mode)
-                hipLaunchKernelGGL((dgs::sort_tiles_lds_kernel<16384>), dim3(il.ntiles), dim3(256), 0, stream, (const uint2*)ranges,
-                                   (const uint64_t*)keys, plist, 2048);
-            if (need_global_sort)
-                hipLaunchKernelGGL(dgs::sort_tiles_global_kernel, dim3(il.ntiles < 256 ? il.ntiles : 256), dim3(256), 0, stream, (const uint2*)ranges, il.ntiles,
-                                   (const uint64_t*)keys, (uint64_t*)(bin + bl.scratch), plist, capacity_mode ? 2048 : 16384);
-        }
-        DGS_STAGE("sort_tiles", debug, stream);
+    c.b = BinningView(bl, bin);
+    if (c.R > 0) {
+        if (int e = scatter_keys(c)) return e;
+        if (int e = sort_tiles(c)) return e;
     }
-    if (timed3) {
-        prof_mark_end(ctx, stream, pp3);
+    if (timed) {
+        prof_mark_end(ctx, stream, pp);
         if (ctx->prof.counters)
-            hipLaunchKernelGGL(sum_forward_units_kernel, dim3(64), dim3(256), 0, stream, (const uint32_t*)(geom + gl.total), (const int*)radii, P,
+            hipLaunchKernelGGL(sum_forward_units_kernel, dim3(64), dim3(256), 0, stream, (const uint32_t*)c.g.state, c.radii, P,
                                ctx->prof.counters + 2, ctx->prof.counters + 3);
     }
-
-    // ---- K7 forward blend
-    dgs::BlendFwdArgs fa;
-    fa.ranges = ranges;
-    fa.point_list = (const uint32_t*)(bin + bl.point_list);
-    fa.rec = pa.rec;
-    fa.W = width; fa.H = height; fa.tiles_x = il.tiles_x; fa.tiles_y = il.tiles_y; fa.mode = tile_order;
-    fa.order = (const uint32_t*)(img + il.order_fwd);   // written by scan_tiles_kernel
-    fa.bg = background;
-    fa.final_T = (float*)(img + il.final_T);
-    fa.n_contrib = (uint32_t*)(img + il.n_contrib);
-    fa.tile_last = (uint32_t*)(img + il.tile_last);
-    fa.out_color = out_color;
-    fa.out_others = out_others;
-    int grid = dgs::blend_grid_size(il.tiles_x, il.tiles_y, fa.mode);
-    fa.long_thr = nullptr;
-    if (fa.mode == 3 && ctx->long_tiles.load() && !ctx->grid_limit_fwd.load()) {   // long-tile path (kernels_blend.h): four workgroups for the longest lists
-        fa.long_thr = (const dgs::LongThr*)(img + il.long_thr);
-        grid = dgs::long_grid_size(il.ntiles);
-    }
-    if (const int lim = ctx->grid_limit_fwd.load()) {
-        grid = lim < grid ? lim : grid;
-        DGS_HIP(hipMemsetAsync(img + il.final_T, 0, il.ranges - il.final_T, stream));   // final_T, n_contrib of the skipped tiles
-        DGS_HIP(hipMemsetAsync(img + il.tile_last, 0, (size_t)il.ntiles * 4, stream));
-    }
-    // accumulator rider: 256 workgroups in FRONT of the tile workgroups (they hold a slot for a few microseconds each while the tile
-    // workgroups fill the rest of the chip; at the end of the grid they would lengthen the drain)
-    fa.clear = nullptr; fa.clear_n4 = 0; fa.clear_blocks = 0;
-    fa.clean_flag = (uint32_t*)(geom + gl.total) + 3;
-    {
-        const size_t acc_bytes = (size_t)P * dgs::kAccFloats * 4;
-        if (ctx->acc_rider.load() && !ctx->grid_limit_fwd.load() && tile_order >= 3 && acc_bytes % 16 == 0 && acc_bytes / 16 < 0xf0000000ull) {
-            fa.clear = (float4*)(geom + gl.acc);
-            fa.clear_n4 = (uint32_t)(acc_bytes / 16);
-            fa.clear_blocks = (int)std::min<size_t>(256, ((fa.clear_n4 + 16 * dgs::kTilePix - 1) / (16 * dgs::kTilePix) + 7) / 8 * 8);   // ~16 stores per thread
-            grid += fa.clear_blocks;
-        }
-    }
-    Prof::Pair pp;
-    const bool timed = prof_begin(ctx, 0, stream, pp);
-    hipLaunchKernelGGL(dgs::blend_fwd_rows_kernel, dim3(grid), dim3(dgs::kTilePix), 0, stream, fa);
-    if (timed) prof_end(ctx, stream, pp, fa.tile_last, il.ntiles);
-    DGS_STAGE("blend_fwd", debug, stream);
-    return R;
+    if (int e = blend_fwd(c, width, height, background, out_color, out_others)) return e;
+    return c.R;
 }
 
 int dgs_context_backward(dgs_context* ctx, int P, int D, int M, int R, const float* background, int width, int height, const float* means3D,
@@ -830,136 +1038,19 @@ int dgs_context_backward(dgs_context* ctx, int P, int D, int M, int R, const flo
     if (shs && colors_precomp == nullptr && !dL_dsh) return fail(DGS_ERR_INVALID_ARGUMENT, "dL_dsh is NULL");
     if (D < 0) D = 0;
 
-    GeomLayout gl(P);
-    ImageLayout il(width, height);
-    BinningLayout bl(R, false);  // only point_list is needed; its offset does not depend on the scratch
-    if (!radii) radii = (const int*)(geom_buffer + gl.internal_radii);
+    const GeomLayout gl(P);
+    const ImageLayout il(width, height);
+    const Options opt = read_options(ctx, il);
+    Pass c{ctx, stream, debug, opt, P, radii, gl, il, GeomView(gl, geom_buffer), ImageView(il, img_buffer)};
+    if (!radii) c.radii = c.g.internal_radii;
+    c.R = R;
+    if (R > 0) c.b = BinningView(BinningLayout(R, false), binning_buffer);  // only point_list is needed; its offset does not depend on the scratch
 
-    const dgs::Camera cam = make_camera(viewmatrix, campos, width, height, tan_fovx, tan_fovy);
-
-    float* acc = (float*)(geom_buffer + gl.acc);
-    const size_t acc_bytes = (size_t)P * dgs::kAccFloats * 4;
-    int bwd_mode = ctx->tile_order.load();
-    if (bwd_mode == 4 && dgs::order_groups(il.tiles_x, il.tiles_y) > dgs::kOrderMaxGroups) bwd_mode = 3;
-    // accumulator rows cleared and (modes 3, 4) the tiles ordered by the traversed length the forward measured: one launch
-    const bool prep_fused = R > 0 && bwd_mode >= 3 && acc_bytes % 16 == 0 && (reinterpret_cast<size_t>(acc) & 15) == 0;
-    if (prep_fused) {
-        const size_t n4 = acc_bytes / 16;
-        const int fill_blocks = (int)std::min<size_t>(1024, (n4 + 4 * 1024 - 1) / (4 * 1024));   // ~4 stores of 16 B per thread
-        hipLaunchKernelGGL(dgs::prep_bwd_kernel, dim3(fill_blocks + 1), dim3(1024), 0, stream, (float4*)acc, n4,
-                           (const uint32_t*)(img_buffer + il.tile_last), il.tiles_x, il.tiles_y, bwd_mode,
-                           (uint32_t*)(img_buffer + il.order_bwd), (uint32_t*)(img_buffer + il.group_xcd), (uint32_t*)(img_buffer + il.long_thr), (uint32_t)ctx->long_div_bwd.load(),
-                           (const uint32_t*)(geom_buffer + gl.total) + 3);   // (the forward rider's flag; blend_bwd_kernel resets it)
-        DGS_STAGE("prep_bwd", debug, stream);
-    } else {
-        DGS_HIP(hipMemsetAsync(acc, 0, acc_bytes, stream));
-    }
-
-    // ---- K8 backward blend
-    if (R > 0) {
-        dgs::BlendBwdArgs ba;
-        ba.ranges = (const uint2*)(img_buffer + il.ranges);
-        ba.point_list = (const uint32_t*)(binning_buffer + bl.point_list);
-        ba.rec = (const float4*)(geom_buffer + gl.rec);
-        ba.W = width; ba.H = height; ba.tiles_x = il.tiles_x; ba.tiles_y = il.tiles_y; ba.mode = ctx->tile_order.load();
-        ba.order = (const uint32_t*)(img_buffer + il.order_bwd);
-        if (ba.mode == 4 && dgs::order_groups(il.tiles_x, il.tiles_y) > dgs::kOrderMaxGroups) ba.mode = 3;
-        if (ba.mode >= 3 && !prep_fused) {  // by the traversed length the forward measured
-            hipLaunchKernelGGL(dgs::tile_order_kernel, dim3(1), dim3(1024), 0, stream, (const uint2*)nullptr,
-                               (const uint32_t*)(img_buffer + il.tile_last), il.tiles_x, il.tiles_y, ba.mode,
-                               (uint32_t*)(img_buffer + il.order_bwd), (uint32_t*)(img_buffer + il.group_xcd));
-            DGS_STAGE("tile_order_bwd", debug, stream);
-        }
-        ba.bg = background;
-        ba.final_T = (const float*)(img_buffer + il.final_T);
-        ba.n_contrib = (const uint32_t*)(img_buffer + il.n_contrib);
-        ba.tile_last = (const uint32_t*)(img_buffer + il.tile_last);
-        ba.dL_dpix = dL_dpix;
-        ba.dL_dothers = dL_depths;
-        ba.acc = acc;
-        ba.clean_flag = (uint32_t*)(geom_buffer + gl.total) + 3;
-        int grid = dgs::blend_grid_size(il.tiles_x, il.tiles_y, ba.mode);
-        ba.long_thr = nullptr;
-        if (ba.mode == 3 && prep_fused && ctx->long_tiles.load() && !ctx->grid_limit_bwd.load()) {   // long-tile path (kernels_blend.h)
-            ba.long_thr = (const dgs::LongThr*)(img_buffer + il.long_thr);
-            grid = dgs::long_grid_size(il.ntiles);
-        }
-        if (const int lim = ctx->grid_limit_bwd.load()) grid = lim < grid ? lim : grid;
-        Prof::Pair pp;
-        const bool timed = prof_begin(ctx, 1, stream, pp);
-        const int det = ctx->deterministic.load();
-        if (det == 2) {
-            // fixed-point sums with integer atomics: order-free, capturable.  The rows live in the context (zero between backward
-            // passes: fixed_to_acc_kernel clears what it converts); they are (re)allocated outside a capture only
-            {
-                std::lock_guard<std::mutex> lk(ctx->mu);
-                if (ctx->acc64_rows < (size_t)P) {
-                    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-                    (void)hipStreamIsCapturing(stream, &cs);
-                    if (cs != hipStreamCaptureStatusNone)
-                        return fail(DGS_ERR_INVALID_ARGUMENT, "deterministic backward (option 7 = 2): the fixed-point rows must exist before a capture (run one eager backward at this size first)");
-                    DGS_HIP(hipStreamSynchronize(stream));
-                    //  the outgrown rows are RETIRED, not freed: a graph captured at the smaller size has their address baked
-                    // in and may still be replayed (its sums then land in rows nobody converts -- a stale graph, but not a write into
-                    // freed memory).  Two backward passes on different streams of ONE context would still share the live rows: callers
-                    // that run views concurrently give each its own context (diff_surfel_rasterization.Lane).
-                    if (ctx->acc64) ctx->acc64_retired.push_back(ctx->acc64);
-                    ctx->acc64 = nullptr; ctx->acc64_rows = 0;
-                    const size_t rows = (size_t)P + (size_t)P / 4 + 1024;
-                    DGS_HIP(hipMalloc((void**)&ctx->acc64, rows * dgs::kAccFloats * sizeof(unsigned long long)));
-                    DGS_HIP(hipMemset(ctx->acc64, 0, rows * dgs::kAccFloats * sizeof(unsigned long long)));
-                    ctx->acc64_rows = rows;
-                }
-            }
-            ba.det_part = nullptr;
-            ba.acc64 = ctx->acc64;
-            hipLaunchKernelGGL(dgs::blend_bwd_kernel<2>, dim3(grid), dim3(dgs::kTilePix), 0, stream, ba);
-            const size_t n = (size_t)P * dgs::kAccFloats;
-            hipLaunchKernelGGL(dgs::fixed_to_acc_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ctx->acc64, acc, n);
-        } else if (det == 1) {
-            // test option: every (list entry, wave) stores its sums in a row of its own, a per-surfel kernel adds them in a fixed
-            // order.  R x 320 bytes of scratch from the stream-ordered allocator (not capturable: tests run eagerly)
-            float* part = nullptr;
-            const size_t bytes = (size_t)R * dgs::kDetRows * dgs::kAccFloats * sizeof(float);
-            DGS_HIP(hipMallocAsync((void**)&part, bytes, stream));
-            DGS_HIP(hipMemsetAsync(part, 0, bytes, stream));
-            ba.det_part = part;
-            hipLaunchKernelGGL(dgs::blend_bwd_kernel<1>, dim3(grid), dim3(dgs::kTilePix), 0, stream, ba);
-            hipLaunchKernelGGL(dgs::det_reduce_kernel, dim3((P + 255) / 256), dim3(256), 0, stream, P, radii,
-                               (const uint2*)(geom_buffer + gl.rects), il.tiles_x, ba.ranges, ba.point_list, (const float*)part, acc);
-            DGS_HIP(hipFreeAsync(part, stream));
-        } else {
-            ba.det_part = nullptr;
-            ba.acc64 = nullptr;
-            hipLaunchKernelGGL(dgs::blend_bwd_kernel<0>, dim3(grid), dim3(dgs::kTilePix), 0, stream, ba);
-        }
-        if (timed) prof_end(ctx, stream, pp, ba.tile_last, il.ntiles);
-        DGS_STAGE("blend_bwd", debug, stream);
-    }
-
-    // ---- K9 + K10 fused per-surfel backward
-    dgs::SurfelBwdArgs sa;
-    sa.P = P; sa.D = D; sa.M = M;
-    sa.means3D = means3D; sa.scales = scales; sa.rotations = rotations;
-    sa.shs = colors_precomp ? nullptr : shs;
-    sa.cam = cam;
-    sa.radii = radii;
-    sa.rec = (const float4*)(geom_buffer + gl.rec);
-    sa.acc = acc;
-    sa.dL_dmean2D = dL_dmean2D; sa.dL_dnormal = dL_dnormal; sa.dL_dopacity = dL_dopacity; sa.dL_dcolor = dL_dcolor;
-    sa.dL_dmean3D = dL_dmean3D; sa.dL_dtransMat = dL_dtransMat; sa.dL_dsh = dL_dsh; sa.sh_all_rows = ctx->sh_all_rows.load(); sa.dL_dscale = dL_dscale; sa.dL_drot = dL_drot;
-    size_t sh_lds = 0;
-    if (sa.shs) {
-        if (M * 3 > 48) return fail(DGS_ERR_INVALID_ARGUMENT, "backward: more than 16 SH coefficients per channel");
-        sa.row_inv = (unsigned)(0xFFFFFFFFu / (unsigned)(M * 3)) + 1u;
-        sh_lds = (size_t)dgs::kSurfelBlock * (M * 3 + 1) * sizeof(float);
-    }
-    Prof::Pair pp4;
-    const bool timed4 = prof_begin(ctx, 4, stream, pp4);
-    hipLaunchKernelGGL(dgs::surfel_bwd_kernel, dim3(gl.nblocks), dim3(dgs::kSurfelBlock), sh_lds, stream, sa);
-    if (timed4) prof_mark_end(ctx, stream, pp4);
-    DGS_STAGE("surfel_bwd", debug, stream);
-    return DGS_OK;
+    if (int e = prep_bwd(c)) return e;
+    if (R > 0)
+        if (int e = blend_bwd(c, width, height, background, dL_dpix, dL_depths)) return e;
+    return surfel_bwd(c, D, M, means3D, scales, rotations, colors_precomp ? nullptr : shs, make_camera(viewmatrix, campos, width, height, tan_fovx, tan_fovy),
+                      dL_dmean2D, dL_dnormal, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dtransMat, dL_dsh, dL_dscale, dL_drot);
 }
 
 

@@ -87,7 +87,7 @@ __device__ __forceinline__ float wave_reduce8_dpp(float (&v)[8])
 // of the 256-byte bank row: conflict free.  (One round of 16 values through 4 KB -- lane l = 4 k + p, four reads, 17 VALU
 // instructions -- was slower for the occupancy its LDS costs: DESIGN.md section 4.)
 // On return lanes 8 k .. 8 k + 3 hold the wave total of v[k] and lanes 8 k + 4 .. 8 k + 7 that of v[k + 8] (reduce16_slot in
-// kernels_blend.h).
+// blend_bwd_kernels.h).
 typedef float red_f32x4 __attribute__((ext_vector_type(4)));
 
 struct RedLds {

@@ -409,7 +409,7 @@ class CaptureMixin:
         backward blend and the skinning backward's node table add 64-bit fixed-point numbers (units of 2^-44) with INTEGER atomics
         (rasterizer option 7 = 2; dgs_deform_backward accumulate bit 4) instead of float atomics.  Two runs from the same seed then agree
         bit for bit through densification and opacity resets (tests/test_learning_gpu.py).  Costs ~5-10 % of a step and quantises
-        the blend's partial sums to 6e-14 (a different, equally valid optimisation: kernels_blend.h).  The option lives in the
+        the blend's partial sums to 6e-14 (a different, equally valid optimisation: blend_bwd_kernels.h).  The option lives in the
         rasterizer context of this trainer's DEVICE; a captured step is re-captured."""
         from diff_surfel_rasterization import _C
         on = bool(on)

@@ -101,7 +101,7 @@ class GuardMixin:
         if not self._graph or self._capacity <= 0:
             raise RuntimeError("rasterizer capacity overflow outside capacity mode")
         self.iteration -= redo          # the skipped steps changed nothing: their views are rendered again
-        # kernels_preprocess.h overflow_reason: 1 capacity, 2 promised list length, 4 beyond the segmented sort -- the bits of EVERY rank's
+        # binning_kernels.h overflow_reason: 1 capacity, 2 promised list length, 4 beyond the segmented sort -- the bits of EVERY rank's
         # flag (the step's MAX all-reduce only says that some rank overflowed, and max(1, 2) drops a bit): all ranks must move to the
         # same capacity and the same promise, or their captures -- and the collectives inside the capture's warm-up steps -- diverge
         reason = self._agree_reason(int(self._oflag.item()))

@@ -19,7 +19,8 @@ _CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # of the scalar forms (no throughput gain) plus v_mov shuffles to pair the operands; measured -17 % / -19 % on the
 # forward / backward blend kernels without it.
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-fno-slp-vectorize"]
-_SOURCES = ["surfel_rasterizer.hip", "kernels_blend.h", "kernels_preprocess.h", "surfel_math.h", "wave_reduce.h"]
+_SOURCES = ["surfel_rasterizer.hip", "blend_common.h", "tile_order_kernels.h", "blend_fwd_kernels.h", "blend_bwd_kernels.h", "surfel_kernels.h",
+            "binning_kernels.h", "tile_sort_kernels.h", "surfel_math.h", "wave_reduce.h"]
 _INPUTS = [os.path.join(_CSRC, s) for s in _SOURCES] + [os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dgs_surfel_rasterizer.h")]
 
 _ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)

@@ -181,6 +181,24 @@ void dgs_set_tight_rects(int on);
  * key 4 / key 5 = diagnostic: the backward / forward blend processes only the first `value` tiles of its dispatch order
  *         (0 = all); results are then incomplete -- for measuring how long the heaviest tiles run on an otherwise idle device.
  * Returns DGS_OK or an error. */
+enum dgs_option {   /* names of the keys above */
+    DGS_OPT_TIGHT_RECTS = 0,
+    DGS_OPT_TILE_ORDER = 1,
+    DGS_OPT_CAPACITY = 2,
+    DGS_OPT_TILE_SORT = 3,
+    DGS_OPT_GRID_LIMIT_BWD = 4,
+    DGS_OPT_GRID_LIMIT_FWD = 5,
+    DGS_OPT_LIST_HINT = 6,
+    DGS_OPT_DETERMINISTIC = 7,
+    DGS_OPT_SH_ALL_ROWS = 8,
+    DGS_OPT_LONG_TILES = 9,
+    DGS_OPT_LONG_DIV_FWD = 10,
+    DGS_OPT_LONG_DIV_BWD = 11,
+    DGS_OPT_MERGED_OFFSETS = 12,
+    DGS_OPT_ORDER_RIDER = 13,
+    DGS_OPT_ACC_RIDER = 14,
+    DGS_OPT_COUNT = 15   /* the number of keys, not a key */
+};
 int dgs_set_option(int key, int value);
 /* The current value of an option of the calling thread's device's default context (>= 0), or a negative status: a caller that
  * switches an option for a while puts back what it found (the context is shared by everything that renders on the device). */

@@ -571,7 +571,7 @@ def _clustered_case(P=7000, n_cluster=3000, H=128, W=160, seed=51):
 
 def test_long_tile_path_matches_the_serial_walk_and_the_oracle():
     """dgs_set_option(9, .): the longest tiles are rendered by four workgroups (one per quadrant, four list quarters per workgroup,
-    kernels_blend.h "long tiles") instead of one.  Against the serial walk of the same lists the result may differ in rounding only
+    blend_common.h "long tiles") instead of one.  Against the serial walk of the same lists the result may differ in rounding only
     (T at the quarter boundaries is a product of products, the sums are added quarter by quarter); against the oracle it meets the
     same bounds; two runs are bit-identical."""
     from diff_surfel_rasterization import _C

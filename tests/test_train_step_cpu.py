@@ -329,7 +329,7 @@ def test_list_promise_moves_up_one_tier_at_a_time():
 
 
 def test_overflow_reason_bits_pick_the_next_configuration_in_one_recovery():
-    """Trainer._after_overflow: the kernels leave the REASON of an overflow in the flag (kernels_preprocess.h overflow_reason: bit 0
+    """Trainer._after_overflow: the kernels leave the REASON of an overflow in the flag (binning_kernels.h overflow_reason: bit 0
     capacity, bit 1 promised list length, bit 2 list beyond the segmented sort's 57 344 entries), so one recovery lands on the
     configuration that fits -- a capacity overflow doubles the capacity and keeps the promise (rounds 3-4 walked the tiers first: up to
     three skipped steps), a broken promise moves the tier and keeps the capacity, a 60 000-entry list goes straight to 'no promise'."""

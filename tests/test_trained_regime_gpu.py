@@ -1,6 +1,6 @@
 """-m gpu: oracle parity in the DENSIFIED regime at the library's default thresholds.  The synthetic clouds of the
 other parity tests have uniform tile lists (mean 772 entries at the metric size), so the long-tile path -- four workgroups sharing the
-list of a tile longer than R/400 (forward) / S/512 (backward) entries, kernels_blend.h -- never engages there unless a test forces its
+list of a tile longer than R/400 (forward) / S/512 (backward) entries, blend_common.h -- never engages there unless a test forces its
 thresholds down.  A fitted scene is where it runs by default: ~86 k surfels crowded onto two surfaces, lists of 1-2 k entries in the
 covered third of the image and none elsewhere.  The scene is regenerated here from its recipe (bench.trained_trainer: seed 0, 10 000
 iterations of the deterministic fit -- bit-reproducible, profiles/r05_bench_line_trained*.json), its assembled rasterizer inputs at two
