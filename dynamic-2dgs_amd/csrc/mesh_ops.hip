@@ -1,12 +1,14 @@
 // libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion of rendered depth maps, marching tetrahedra, the all-pairs
-// nearest-neighbour and closest-triangle searches of the mesh metrics, the z-buffer triangle rasterizer of the mesh images and the
-// connected components of the mesh clean-up, gfx950.
+// nearest-neighbour and closest-triangle searches and the earth mover's distance (an auction solver) of the mesh metrics, the
+// z-buffer triangle rasterizer of the mesh images and the connected components of the mesh clean-up, gfx950.
 // Compiled with -ffp-contract=off: every fp32 operation of the kernels rounds on its own, which is what makes the result equal to
 // the PyTorch statement of the same arithmetic (dgs_amd/mesh.py) instead of close to it.
 // The kernels live in one header per family, included in the order they were written; this file is the C ABI: the argument checks
 // and the launches.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <string>
 
 #include "../../include/dgs_mesh_ops.h"
@@ -153,6 +155,103 @@ int dgs_tri_search(long long n_query, const float* query, long long n_tri, const
 }
 
 int dgs_tri_layout(int out[4]) { return layout("dgs_tri_layout", out, {TRI_Q, TRI_T, TRI_CHUNK, TRI_ROW}); }
+
+int dgs_emd_auction(long long n, const float* a, const float* b, float inv_q, long long max_rounds, void* scratch, long long scratch_bytes,
+                    int* assignment, long long* prices, long long* result, void* stream) {
+    const std::string w = "dgs_emd_auction";
+    if (!result) return fail(-1, w + ": null pointer (result)");
+    for (int k = 0; k < EMD_RESULTS; ++k) result[k] = 0;
+    if (n < 0) return fail(-1, w + ": negative n");
+    if (n >= (1LL << EMD_BIDDER_BITS)) return fail(-1, w + ": n must be below 2^24 (the bidder is the low 24 bits of the packed bid)");
+    if (max_rounds <= 0) return fail(-1, w + ": max_rounds must be >= 1");
+    if (!(inv_q >= 0.0f) || inv_q > 3.0e38f) return fail(-1, w + ": inv_q must be finite and >= 0");
+    if (n == 0) return 0;
+    if (!a || !b || !assignment || !prices) return fail(-1, w + ": null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e;
+    auto hip_failed = [&](const char* what) { return fail(-2, w + " (" + what + "): " + hipGetErrorString(e)); };
+    if (n == 1) {                                                          // no second best: the trivial matching, nothing launched
+        float pa[3], pb[3];
+        if ((e = hipMemcpyAsync(pa, a, sizeof pa, hipMemcpyDeviceToHost, st)) != hipSuccess) return hip_failed("read a");
+        if ((e = hipMemcpyAsync(pb, b, sizeof pb, hipMemcpyDeviceToHost, st)) != hipSuccess) return hip_failed("read b");
+        if ((e = hipMemsetAsync(assignment, 0, sizeof(int), st)) != hipSuccess) return hip_failed("assignment");
+        if ((e = hipMemsetAsync(prices, 0, sizeof(long long), st)) != hipSuccess) return hip_failed("prices");
+        if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_failed("synchronise");
+        const float dx = pa[0] - pb[0], dy = pa[1] - pb[1], dz = pa[2] - pb[2];   // emd_cost on the host (this file is built with
+        const float d = std::sqrt((dx * dx + dy * dy) + dz * dz);                 // -ffp-contract=off for the host too)
+        result[0] = result[1] = (long long)std::fmin(std::nearbyint(d * inv_q), EMD_COST_CAP);
+        return 0;
+    }
+    if (!scratch) return fail(-1, w + ": null pointer (scratch)");
+    if ((size_t)scratch % 8 != 0) return fail(-1, w + ": the scratch buffer must be 8-byte aligned");
+    if (scratch_bytes < EMD_SCRATCH_FIXED + n * EMD_SCRATCH_PER_POINT)
+        return fail(-1, w + ": the scratch buffer is too small (" + std::to_string(EMD_SCRATCH_FIXED) + " + " + std::to_string(EMD_SCRATCH_PER_POINT) +
+                            " bytes per point are needed, dgs_emd_layout)");
+    // scratch: control block | word [n] u64 | mine [n] u64 | owner, target, list0, list1 [n] int32 each
+    EmdState s;
+    s.n = (int)n, s.inv_q = inv_q, s.a = a, s.b = b, s.price = prices, s.assign = assignment;
+    s.ctrl = reinterpret_cast<EmdCtrl*>(scratch);
+    s.word = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(scratch) + EMD_SCRATCH_FIXED);
+    s.mine = s.word + n;
+    s.owner = reinterpret_cast<int*>(s.mine + n), s.target = s.owner + n, s.list0 = s.target + n, s.list1 = s.list0 + n;
+    EmdCtrl h;
+    auto read_ctrl = [&]() {
+        if ((e = hipMemcpyAsync(&h, s.ctrl, sizeof h, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+        return e = hipStreamSynchronize(st);
+    };
+    // the control block and the words start at 0 (the two are adjacent), the prices too
+    if ((e = hipMemsetAsync(scratch, 0, EMD_SCRATCH_FIXED + (size_t)n * sizeof(unsigned long long), st)) != hipSuccess) return hip_failed("init");
+    if ((e = hipMemsetAsync(prices, 0, (size_t)n * sizeof(long long), st)) != hipSuccess) return hip_failed("init");
+    const dim3 threads(EMD_THREADS);
+    const unsigned per_point = (unsigned)((n + EMD_THREADS - 1) / EMD_THREADS);
+    const unsigned per_wave = (unsigned)std::min<long long>((n + EMD_WAVES - 1) / EMD_WAVES, EMD_MAX_BLOCKS);
+    hipLaunchKernelGGL(emd_max_cost_kernel, dim3(per_wave), threads, 0, st, s);
+    if (int rc = launched("dgs_emd_auction (max cost)")) return rc;
+    if (read_ctrl() != hipSuccess) return hip_failed("max cost");
+    long long eps = std::max<long long>(1, h.max_cost / 2), rounds = 0;
+    int phase = 0;
+    for (;; ++phase) {
+        hipLaunchKernelGGL(emd_phase_kernel, dim3(per_point), threads, 0, st, s);
+        long long bidders = n;                                             // an upper bound for the whole phase: the count never grows
+        for (int cur = 0; bidders > 0;) {
+            const long long left = max_rounds - rounds;
+            if (left <= 0) {
+                result[2] = rounds, result[3] = h.max_cost, result[4] = phase, result[5] = eps, result[6] = bidders;
+                return fail(-3, w + ": max_rounds = " + std::to_string(max_rounds) + " reached in phase " + std::to_string(phase) + " (eps " +
+                                    std::to_string(eps) + ") with " + std::to_string(bidders) + " of " + std::to_string(n) + " still unassigned");
+            }
+            const bool dense = bidders > EMD_SPARSE_MAX;
+            const long long batch = std::min<long long>(left, dense ? EMD_DENSE_BATCH : EMD_SPARSE_BATCH);
+            const dim3 bid_grid((unsigned)(dense ? (bidders + EMD_THREADS - 1) / EMD_THREADS : bidders));   // sparse: a workgroup per bidder
+            const dim3 resolve_grid((unsigned)((bidders + EMD_THREADS - 1) / EMD_THREADS));
+            for (long long r = 0; r < batch; ++r, cur ^= 1) {              // rounds after the phase has converged are no-ops
+                if (dense)
+                    hipLaunchKernelGGL(emd_bid_dense_kernel, bid_grid, threads, 0, st, s, cur, eps);
+                else
+                    hipLaunchKernelGGL(emd_bid_sparse_kernel, bid_grid, threads, 0, st, s, cur, eps);
+                hipLaunchKernelGGL(emd_resolve_kernel, resolve_grid, threads, 0, st, s, cur);
+            }
+            if (int rc = launched("dgs_emd_auction (round)")) return rc;
+            if (read_ctrl() != hipSuccess) return hip_failed("round");
+            if (h.status != 0) return fail(-4, w + ": a bid of phase " + std::to_string(phase) + " does not fit 39 bits");
+            bidders = h.count[cur], rounds = h.rounds;
+        }
+        if (eps == 1) break;
+        eps = std::max<long long>(1, eps / 4);
+    }
+    if ((e = hipMemsetAsync(assignment, 0xFF, (size_t)n * sizeof(int), st)) != hipSuccess) return hip_failed("assignment");
+    hipLaunchKernelGGL(emd_assign_kernel, dim3(per_point), threads, 0, st, s);
+    hipLaunchKernelGGL(emd_sums_kernel, dim3(per_wave), threads, 0, st, s);
+    if (int rc = launched("dgs_emd_auction (sums)")) return rc;
+    if (read_ctrl() != hipSuccess) return hip_failed("sums");
+    if (h.status != 0) return fail(-5, w + ": the owners are not a permutation at the end");
+    result[0] = h.primal, result[1] = h.sum_min - h.sum_price, result[2] = h.rounds, result[3] = h.max_cost, result[4] = phase + 1, result[5] = eps;
+    return 0;
+}
+
+int dgs_emd_layout(int out[6]) {
+    return layout("dgs_emd_layout", out, {EMD_THREADS, EMD_T, EMD_SPARSE_MAX, EMD_RESULTS, EMD_SCRATCH_FIXED, EMD_SCRATCH_PER_POINT});
+}
 
 int dgs_mesh_raster(long long n_faces, const float* table, const int* list, long long n_list, int path, int H, int W,
                     unsigned long long* best, int clear, void* stream) {

@@ -1,5 +1,6 @@
-// mesh_search_kernels.h -- the two all-pairs searches of the mesh metrics (mesh_ops.hip: dgs_nn_search, dgs_tri_search).  The two
-// kernels share their shape and nothing else: each keeps its own statement of the query state and the packed-minimum commit.
+// mesh_search_kernels.h -- the all-pairs searches of the mesh metrics (mesh_ops.hip: dgs_nn_search, dgs_tri_search and, at the end,
+// the kernels of dgs_emd_auction).  The first two kernels share their shape and nothing else: each keeps its own statement of the
+// query state and the packed-minimum commit; the auction's bidding pass keeps a top-2 and is described with its kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -145,6 +146,268 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_search_kernel(long long n_que
         const long long q = q0 + (long long)k * TRI_THREADS;
         if (q < n_query)
             atomicMin(&best[q], ((unsigned long long)__float_as_uint(bd[k]) << 32) | (unsigned long long)(unsigned)(f_begin + bi[k]));
+    }
+}
+
+// ---- earth mover's distance: the auction ------------------------------------------------------------------------------------------
+// The third all-pairs search (dgs_emd_auction; include/dgs_mesh_ops.h states the quantity and the schedule, dgs_amd/mesh_metrics.py:
+// emd_torch is the same statement in PyTorch).  Per unassigned person i, over ALL objects j: the smallest and the second smallest
+// w = c_ij + p_j and the lowest j of the smallest -- a top-2 where nn_search_kernel keeps a top-1, with an integer price per point.
+// Everything the auction iterates on is an integer: c_ij is an int in [0, 2^20], prices, bids and w are 64-bit.
+//   packed word of an object = bid << 24 | bidder:  bidder < n < 2^24, bid < 2^39, the word below 2^63 like the packed minima above (a bid that would not fit raises the status flag
+//   and is not placed).  The words are never cleared: a bid exceeds the price it is placed on (eps >= 1), the price is the last
+//   winning bid, so every later word on an object is larger than every earlier one and an earlier one can never equal a new one.
+// One round = two launches, the host enqueues them in batches (no kernel waits for another workgroup):
+//   bid      every person of list[cur] finds its top-2 against the prices as they stand (nobody writes a price in this launch),
+//            places atomicMax(word[j1], packed) and remembers (packed, j1);
+//   resolve  every person of list[cur] looks at word[j1]: equal to its own packed word = it won (price, owner updated; the evicted
+//            owner goes to list[cur ^ 1]), else it goes to list[cur ^ 1] itself.  Exactly one person wins an object, so owner[j] and
+//            price[j] have one writer.  The order of a list depends on scheduling, nothing computed from it does.
+// A round whose list is empty changes nothing (the bid launch only zeroes the other list's count, which is already 0), so rounds
+// enqueued after a phase has converged are no-ops; `rounds` counts the launches that had bidders.
+// Two bidding kernels, the same numbers (the host picks by the bidder count at the start of a batch; within a phase the count never
+// grows: a round assigns as many persons as it evicts, or more):
+//   dense   a thread per bidder (state in registers: coordinates, w1, j1, w2), the objects (x | y | z planes and the prices) staged
+//           through LDS in rounds of EMD_T and read with 16-byte loads at an address every lane shares: a broadcast, as in
+//           nn_search_kernel.  12 KB + 8 KB of LDS, 256 threads: occupancy is not the limit, the bidder count is -- the objects are
+//           not sliced over workgroups (a packed minimum cannot carry a top-2, and the rounds that would need it are a handful).
+//   sparse  a workgroup per bidder: thread t takes objects t, t + 256, ... straight from global memory (the whole set is n x 20
+//           bytes, it lives in L2); a wave merges its 64 records by a butterfly of shuffles, the four waves meet in 96 bytes of LDS.
+//           The walk is a chain of L2 round trips, so a round costs n / 256 of them (a wave per bidder, measured first, took 13 / 20 /
+//           33 us per round at n = 2048 / 4096 / 8192: four times the trips).  EMD_SPARSE_MAX = 768 bidders are 768 workgroups = three
+//           per CU, all resident at once.
+// Per pair: 3 subtractions, 3 multiplications, 2 additions, a correctly rounded sqrt, multiply, rint, min, convert, a 64-bit add,
+// two 64-bit compares and five selects.
+constexpr int EMD_THREADS = 256, EMD_WAVES = EMD_THREADS / 64, EMD_T = 1024, EMD_SPARSE_MAX = 768;
+constexpr int EMD_BIDDER_BITS = 24, EMD_BID_BITS = 39, EMD_MAX_BLOCKS = 1024;
+constexpr float EMD_COST_CAP = 1048576.0f;                                   // 2^20
+// the host's side (mesh_ops.hip): rounds per batch -- one read of the control block ends a batch; a phase leaves the dense rounds
+// within a few of them, its sparse tail is hundreds to thousands long -- and the sizes of the caller's scratch and result arrays
+constexpr int EMD_DENSE_BATCH = 4, EMD_SPARSE_BATCH = 64, EMD_RESULTS = 8, EMD_SCRATCH_FIXED = 64, EMD_SCRATCH_PER_POINT = 32;
+
+struct EmdCtrl {                    // device-side control block, 64 bytes, zeroed by the host before the first launch
+    int count[2];                   // persons in list[0], list[1]
+    int status;                     // != 0: a bid did not fit EMD_BID_BITS
+    int max_cost;                   // max c_ij (emd_max_cost_kernel)
+    long long rounds;               // rounds that had bidders
+    long long primal, sum_min, sum_price;   // emd_sums_kernel
+    long long pad[2];
+};
+static_assert(sizeof(EmdCtrl) == EMD_SCRATCH_FIXED, "the control block is the fixed part of the scratch buffer");
+
+struct EmdState {
+    int n;
+    float inv_q;
+    const float *a, *b;             // [n,3] persons, objects
+    long long* price;               // [n]
+    unsigned long long *word, *mine;   // [n] per object: the largest packed bid so far;  [n] per person: its packed bid of this round (0: none)
+    int *owner, *target, *assign;   // [n] object -> person or -1;  person -> the object it bid on;  person -> object (written at the end)
+    int *list0, *list1;             // [n] each: the unassigned persons of this round and of the next (emd_list)
+    EmdCtrl* ctrl;
+};
+
+struct EmdTop2 {
+    long long w1, w2;               // smallest and second smallest c + p (over j != j1)
+    int j1;                         // lowest index that attains w1
+};
+
+__device__ __forceinline__ int* emd_list(const EmdState& s, int k) { return k ? s.list1 : s.list0; }
+
+__device__ __forceinline__ EmdTop2 emd_empty() { return EmdTop2{0x7FFFFFFFFFFFFFFFLL, 0x7FFFFFFFFFFFFFFFLL, 0x7FFFFFFF}; }
+
+// c_ij = min(rint(sqrt((dx dx + dy dy) + dz dz) * inv_q), 2^20): every operation rounded on its own, the sqrt correctly rounded
+__device__ __forceinline__ int emd_cost(float ax, float ay, float az, float bx, float by, float bz, float inv_q) {
+    const float dx = ax - bx, dy = ay - by, dz = az - bz;
+    const float d = sqrtf((dx * dx + dy * dy) + dz * dz);              // (the IEEE sqrt; __fsqrt_rn is v_sqrt_f32 here: 1 ulp)
+    return (int)fminf(rintf(d * inv_q), EMD_COST_CAP);
+}
+
+// objects are visited in ascending j: the strict `<` keeps the lowest index among equal w1
+__device__ __forceinline__ void emd_visit(EmdTop2& t, long long w, int j) {
+    const bool first = w < t.w1, second = w < t.w2;
+    t.w2 = first ? t.w1 : (second ? w : t.w2);
+    t.j1 = first ? j : t.j1;
+    t.w1 = first ? w : t.w1;
+}
+
+// the top-2 of the union of two disjoint object sets; symmetric in its arguments
+__device__ __forceinline__ EmdTop2 emd_merge(const EmdTop2& x, const EmdTop2& y) {
+    const bool swap = y.w1 < x.w1 || (y.w1 == x.w1 && y.j1 < x.j1);
+    EmdTop2 lo = swap ? y : x;
+    const long long other = swap ? x.w1 : y.w1;
+    lo.w2 = lo.w2 < other ? lo.w2 : other;
+    return lo;
+}
+
+__device__ __forceinline__ EmdTop2 emd_wave_merge(EmdTop2 t) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        EmdTop2 o;
+        o.w1 = __shfl_xor(t.w1, m, 64), o.w2 = __shfl_xor(t.w2, m, 64), o.j1 = __shfl_xor(t.j1, m, 64);
+        t = emd_merge(t, o);
+    }
+    return t;                                                              // the same record in every lane
+}
+
+// one thread's walk over objects first, first + stride, ... (inside [0, n)) for the person at (ax, ay, az), merged over its wave.
+// Four objects are loaded before the first is used: the loads of a step overlap instead of queueing behind each other's use.
+__device__ __forceinline__ EmdTop2 emd_wave_scan(const EmdState& s, float ax, float ay, float az, int first, int stride) {
+    EmdTop2 t = emd_empty();
+    int j = first;
+    for (; j + 3 * stride < s.n; j += 4 * stride) {
+        float x[4], y[4], z[4];
+        long long p[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k = j + u * stride;                                  // <= j + 3 stride < n
+            x[u] = s.b[3 * k], y[u] = s.b[3 * k + 1], z[u] = s.b[3 * k + 2], p[u] = s.price[k];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) emd_visit(t, (long long)emd_cost(ax, ay, az, x[u], y[u], z[u], s.inv_q) + p[u], j + u * stride);
+    }
+    for (; j < s.n; j += stride)
+        emd_visit(t, (long long)emd_cost(ax, ay, az, s.b[3 * j], s.b[3 * j + 1], s.b[3 * j + 2], s.inv_q) + s.price[j], j);
+    return emd_wave_merge(t);
+}
+
+// the four waves of a workgroup meet in LDS; the result in every thread.  `slot`: EMD_WAVES records of the caller's LDS.
+__device__ __forceinline__ EmdTop2 emd_group_merge(EmdTop2 t, EmdTop2* slot) {
+    __syncthreads();                                                       // the readers of an earlier use are done
+    if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = t;
+    __syncthreads();
+    EmdTop2 r = slot[0];
+#pragma unroll
+    for (int w = 1; w < EMD_WAVES; ++w) r = emd_merge(r, slot[w]);
+    return r;
+}
+
+// n >= 2: j1 is an object and w2 a real value.  bid = p_j1 + (w2 - w1) + eps >= 1.
+__device__ __forceinline__ void emd_place(const EmdState& s, int i, const EmdTop2& t, long long eps) {
+    const long long bid = s.price[t.j1] + (t.w2 - t.w1) + eps;
+    unsigned long long packed = 0;
+    if (bid < (1LL << EMD_BID_BITS)) {
+        packed = ((unsigned long long)bid << EMD_BIDDER_BITS) | (unsigned long long)i;
+        atomicMax(&s.word[t.j1], packed);
+    } else {
+        atomicOr(&s.ctrl->status, 1);
+    }
+    s.mine[i] = packed, s.target[i] = t.j1;
+}
+
+__global__ __launch_bounds__(EMD_THREADS) void emd_bid_dense_kernel(EmdState s, int cur, long long eps) {
+    __shared__ __attribute__((aligned(16))) float pts[3 * EMD_T];
+    __shared__ __attribute__((aligned(16))) long long prc[EMD_T];
+    const int count = s.ctrl->count[cur];                                  // <= n; nobody writes it during this launch
+    if (blockIdx.x == 0 && threadIdx.x == 0) s.ctrl->count[cur ^ 1] = 0;   // the list the resolve launch will fill
+    for (int first = blockIdx.x * EMD_THREADS; first < count; first += gridDim.x * EMD_THREADS) {   // (uniform over the workgroup)
+        const int t = first + threadIdx.x;
+        const bool live = t < count;                                       // a thread past the end computes on person 0 and places nothing
+        const int i = live ? emd_list(s, cur)[t] : 0;
+        const float ax = s.a[3 * i], ay = s.a[3 * i + 1], az = s.a[3 * i + 2];
+        EmdTop2 r = emd_empty();
+        auto visit = [&](float x, float y, float z, long long p, int j) { emd_visit(r, (long long)emd_cost(ax, ay, az, x, y, z, s.inv_q) + p, j); };
+        for (int js = 0; js < s.n; js += EMD_T) {
+            const int m = s.n - js < EMD_T ? s.n - js : EMD_T;            // objects of this round: only they are staged and read
+            __syncthreads();                                               // the previous round's readers are done
+            const float* src = s.b + 3 * js;
+            for (int e = threadIdx.x; e < 3 * m; e += EMD_THREADS) {       // 3 (js + m) <= 3 n: inside the object array
+                const int p = e / 3;
+                pts[(e - 3 * p) * EMD_T + p] = src[e];
+            }
+            for (int e = threadIdx.x; e < m; e += EMD_THREADS) prc[e] = s.price[js + e];
+            __syncthreads();
+            int j = 0;
+            for (; j + 4 <= m; j += 4) {
+                const float4 X = *reinterpret_cast<const float4*>(&pts[j]), Y = *reinterpret_cast<const float4*>(&pts[EMD_T + j]),
+                             Z = *reinterpret_cast<const float4*>(&pts[2 * EMD_T + j]);
+                visit(X.x, Y.x, Z.x, prc[j], js + j), visit(X.y, Y.y, Z.y, prc[j + 1], js + j + 1);
+                visit(X.z, Y.z, Z.z, prc[j + 2], js + j + 2), visit(X.w, Y.w, Z.w, prc[j + 3], js + j + 3);
+            }
+            for (; j < m; ++j) visit(pts[j], pts[EMD_T + j], pts[2 * EMD_T + j], prc[j], js + j);
+        }
+        if (live) emd_place(s, i, r, eps);
+    }
+}
+
+__global__ __launch_bounds__(EMD_THREADS) void emd_bid_sparse_kernel(EmdState s, int cur, long long eps) {
+    const int count = s.ctrl->count[cur];
+    if (blockIdx.x == 0 && threadIdx.x == 0) s.ctrl->count[cur ^ 1] = 0;
+    __shared__ EmdTop2 slot[EMD_WAVES];
+    for (int t = blockIdx.x; t < count; t += gridDim.x) {                  // (uniform over the workgroup: the barriers are met by all)
+        const int i = emd_list(s, cur)[t];
+        const EmdTop2 r = emd_group_merge(emd_wave_scan(s, s.a[3 * i], s.a[3 * i + 1], s.a[3 * i + 2], threadIdx.x, EMD_THREADS), slot);
+        if (threadIdx.x == 0) emd_place(s, i, r, eps);
+    }
+}
+
+__global__ __launch_bounds__(EMD_THREADS) void emd_resolve_kernel(EmdState s, int cur) {
+    const int count = s.ctrl->count[cur];
+    if (blockIdx.x == 0 && threadIdx.x == 0 && count > 0) s.ctrl->rounds += 1;   // (its only writer; read by the host)
+    for (int t = blockIdx.x * EMD_THREADS + threadIdx.x; t < count; t += gridDim.x * EMD_THREADS) {
+        const int i = emd_list(s, cur)[t], j = s.target[i];
+        const unsigned long long packed = s.mine[i];
+        int back = i;                                                      // who is unassigned after this round: the loser itself ...
+        if (packed != 0 && s.word[j] == packed) {
+            s.price[j] = (long long)(packed >> EMD_BIDDER_BITS);
+            back = s.owner[j];                                             // ... or the owner the winner evicts (-1: the object was free)
+            s.owner[j] = i;
+        }
+        if (back >= 0) emd_list(s, cur ^ 1)[atomicAdd(&s.ctrl->count[cur ^ 1], 1)] = back;   // at most `count` <= n appends
+    }
+}
+
+// the start of a phase: nobody assigned, the prices stay
+__global__ __launch_bounds__(EMD_THREADS) void emd_phase_kernel(EmdState s) {
+    const int i = blockIdx.x * EMD_THREADS + threadIdx.x;
+    if (i < s.n) s.owner[i] = -1, s.list0[i] = i;
+    if (i == 0) s.ctrl->count[0] = s.n, s.ctrl->count[1] = 0;
+}
+
+// max c_ij, for the first eps: a wave per person, one atomic per wave
+__global__ __launch_bounds__(EMD_THREADS) void emd_max_cost_kernel(EmdState s) {
+    const int lane = threadIdx.x & 63;
+    int best = 0;
+    for (int i = blockIdx.x * EMD_WAVES + (threadIdx.x >> 6); i < s.n; i += gridDim.x * EMD_WAVES) {
+        const float ax = s.a[3 * i], ay = s.a[3 * i + 1], az = s.a[3 * i + 2];
+        for (int j = lane; j < s.n; j += 64) {
+            const int c = emd_cost(ax, ay, az, s.b[3 * j], s.b[3 * j + 1], s.b[3 * j + 2], s.inv_q);
+            best = c > best ? c : best;
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const int o = __shfl_xor(best, m, 64);
+        best = o > best ? o : best;
+    }
+    if (lane == 0) atomicMax(&s.ctrl->max_cost, best);
+}
+
+__global__ __launch_bounds__(EMD_THREADS) void emd_assign_kernel(EmdState s) {
+    const int j = blockIdx.x * EMD_THREADS + threadIdx.x;
+    if (j < s.n) {
+        const int i = s.owner[j];
+        if (i >= 0 && i < s.n) s.assign[i] = j;                            // (a permutation when the auction has ended)
+    }
+}
+
+// primal = sum_i c_{i, assign(i)};  sum_min = sum_i min_j (c_ij + p_j), the bidding pass's first half;  sum_price = sum_j p_j.
+// Integer sums: a wave adds up its persons in registers and issues three 64-bit atomic adds; any order gives the same integers.
+__global__ __launch_bounds__(EMD_THREADS) void emd_sums_kernel(EmdState s) {
+    const int lane = threadIdx.x & 63;
+    long long primal = 0, sum_min = 0, sum_price = 0;
+    for (int i = blockIdx.x * EMD_WAVES + (threadIdx.x >> 6); i < s.n; i += gridDim.x * EMD_WAVES) {
+        const float ax = s.a[3 * i], ay = s.a[3 * i + 1], az = s.a[3 * i + 2];
+        const EmdTop2 r = emd_wave_scan(s, ax, ay, az, lane, 64);
+        const int j0 = s.assign[i];                                        // -1 (the host's fill) if the owners were no permutation:
+        const int j = (unsigned)j0 < (unsigned)s.n ? j0 : 0;               // flagged, and no address leaves the object array
+        if (j != j0 && lane == 0) atomicOr(&s.ctrl->status, 2);
+        sum_min += r.w1, sum_price += s.price[i];
+        primal += emd_cost(ax, ay, az, s.b[3 * j], s.b[3 * j + 1], s.b[3 * j + 2], s.inv_q);
+    }
+    if (lane == 0) {
+        atomicAdd((unsigned long long*)&s.ctrl->primal, (unsigned long long)primal);
+        atomicAdd((unsigned long long*)&s.ctrl->sum_min, (unsigned long long)sum_min);
+        atomicAdd((unsigned long long*)&s.ctrl->sum_price, (unsigned long long)sum_price);
     }
 }
 

@@ -1,5 +1,5 @@
 """ctypes binding of libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion, marching tetrahedra, the all-pairs nearest-neighbour
-and closest-triangle searches, the z-buffer triangle rasterizer and the connected components for gfx950, used by dgs_amd.mesh,
+and closest-triangle searches, the auction solver of the earth mover's distance, the z-buffer triangle rasterizer and the connected components for gfx950, used by dgs_amd.mesh,
 dgs_amd.mesh_metrics, dgs_amd.mesh_render and dgs_amd.mesh_clean when the data lives on a HIP device.  CPU tensors use the PyTorch /
 NumPy statements in those modules."""
 import ctypes
@@ -31,6 +31,9 @@ _SIGNATURES = {
     "dgs_nn_layout": (_ci, _LAYOUT),
     "dgs_tri_search": (_ci, _SEARCH),
     "dgs_tri_layout": (_ci, _LAYOUT),
+    # earth mover's distance (its kernels close mesh_search_kernels.h)
+    "dgs_emd_auction": (_ci, [_ll, _vp, _vp, _cf, _ll, _vp, _ll, _vp, _vp, _vp, _vp]),
+    "dgs_emd_layout": (_ci, _LAYOUT),
     # triangle rasterizer
     "dgs_mesh_raster": (_ci, [_ll, _vp, _vp, _ll, _ci, _ci, _ci, _vp, _ci, _vp]),
     "dgs_mesh_resolve": (_ci, [_ci, _ci, _vp, _ll, _vp, _vp, _ll, _vp, _ci] + [_vp] * 6),
@@ -168,6 +171,43 @@ def closest_face(points, table, tri_chunk=None):
     layout = tri_layout()
     return _search("closest_face", "dgs_tri_search", layout, tri_chunk, points, "points", table, "table", layout[3],
                    "points [Nq,3] and table [Nf,%d]" % layout[3])
+
+
+def emd_layout():
+    """(threads per workgroup, objects per LDS round of the dense bidding kernel, largest bidder count of the sparse bidding kernel,
+    entries of the result array, fixed bytes of scratch, bytes of scratch per point) of dgs_emd_auction."""
+    return _layout("dgs_emd_layout", 6)
+
+
+EMD_CAP, EMD_OVERFLOW = -3, -4   # statuses of dgs_emd_auction: max_rounds reached; a bid that does not fit 40 bits
+
+
+def emd_auction(a, b, inv_q, max_rounds, scratch=None):
+    """dgs_emd_auction on persons a [n,3] and objects b [n,3] (fp32 HIP tensors) -> (assignment [n] int32, prices [n] int64, primal,
+    dual, rounds, max cost).  inv_q: mesh_metrics._emd_quantum.  scratch: an optional uint8 HIP tensor to reuse (emd_layout gives
+    its size).  RuntimeError when max_rounds is reached (the message names the phase, eps and the bidders left) or a bid overflows."""
+    lib = load()
+    dev = a.device
+    _f32(a, "a"), _f32(b, "b")
+    if b.device != dev:
+        raise RuntimeError("emd_auction: b lives on another device than a")
+    if a.dim() != 2 or a.shape[1] != 3 or b.shape != a.shape:
+        raise RuntimeError("emd_auction: a [n,3] and b [n,3] are expected")
+    n = a.shape[0]
+    lay = emd_layout()
+    need = lay[4] + n * lay[5]
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not (scratch.is_cuda and scratch.device == dev and scratch.dtype == torch.uint8 and scratch.is_contiguous() and scratch.numel() >= need):
+        raise RuntimeError("emd_auction: scratch must be a contiguous uint8 tensor of at least %d bytes on the device of a" % need)
+    assignment = torch.empty(n, dtype=torch.int32, device=dev)
+    prices = torch.empty(n, dtype=torch.int64, device=dev)
+    result = (ctypes.c_longlong * lay[3])()
+    with torch.cuda.device(dev):
+        rc = lib.dgs_emd_auction(n, a.data_ptr(), b.data_ptr(), float(inv_q), int(max_rounds), scratch.data_ptr(), scratch.numel(),
+                                 assignment.data_ptr(), prices.data_ptr(), ctypes.cast(result, ctypes.c_void_p), _stream(dev))
+    _check(lib, rc, "dgs_emd_auction")
+    return assignment, prices, int(result[0]), int(result[1]), int(result[2]), int(result[3])
 
 
 def raster_layout():

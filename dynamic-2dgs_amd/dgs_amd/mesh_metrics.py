@@ -8,6 +8,8 @@ mode="surface" a sample's distance is the exact one to the other SURFACE (the mi
                    arithmetic and the tie rule); CPU tensors: nearest_torch, the PyTorch statement of the same arithmetic
   closest_face     exact point-to-triangle distance to the closest face of a mesh; HIP device: dgs_tri_search over the rows of
                    triangle_table; CPU tensors: closest_face_torch, the PyTorch statement of the same arithmetic
+  emd              earth mover's distance of two equal-sized point sets: a one-to-one matching by an integer auction; HIP device:
+                   dgs_emd_auction; CPU tensors: emd_torch, the PyTorch statement of the same schedule (bit-identical)
   sample_surface   area-weighted uniform samples of a mesh, the same points on every device
   mesh_distance    the metrics of one pair of meshes
   read_mesh        .ply (io.read_mesh_ply) or .obj (io.read_mesh_obj)
@@ -176,6 +178,138 @@ def closest_face(points, vertices, faces, face_chunk=None):
     return _mesh_ops.closest_face(points.float().contiguous(), triangle_table(vertices.float(), faces), face_chunk)
 
 
+# ---- earth mover's distance -------------------------------------------------------------------------------------------------------
+EMD_COST_CAP = 1 << 20     # costs are integers in [0, 2^20]: the bounding-box diagonal of both sets is 2^20 quanta
+EMD_BIDDER_BITS, EMD_BID_BITS = 24, 39   # the packed word of an object: bid << 24 | bidder, below 2^63 (signed = unsigned order)
+
+
+def _emd_quantum(a, b):
+    """(q, inv_q) as Python floats that hold fp32 values: q = diag / 2^20 with diag the fp32 bounding-box diagonal of both sets
+    together, sqrt((ex * ex + ey * ey) + ez * ez) of the fp32 extents; inv_q = 1 / q in fp32, 0 where q is not positive (all
+    points coincide: every cost is 0).  The six extrema are exact on any device; the arithmetic on them runs on the CPU, so the
+    HIP path and the statement are handed the same number."""
+    lo = torch.minimum(a.min(0).values, b.min(0).values).float().cpu()
+    hi = torch.maximum(a.max(0).values, b.max(0).values).float().cpu()
+    e = hi - lo
+    diag = torch.sqrt(((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]).double()).float()    # correctly rounded (see _emd_costs)
+    q = diag / float(EMD_COST_CAP)
+    inv_q = 1.0 / q
+    if not float(q) > 0.0 or not math.isfinite(float(inv_q)):
+        return float(q) if float(q) > 0.0 else 0.0, 0.0
+    return float(q), float(inv_q)
+
+
+def _emd_costs(a, b, inv_q):
+    """[n, n] int64: c_ij = min(rint(sqrt((dx * dx + dy * dy) + dz * dz) * inv_q), 2^20) in fp32, one rounding per operation -- the
+    expression of include/dgs_mesh_ops.h (the kernels recompute it per pair; the statement and the tests may hold the matrix)."""
+    dx, dy, dz = a[:, 0:1] - b[:, 0].unsqueeze(0), a[:, 1:2] - b[:, 1].unsqueeze(0), a[:, 2:3] - b[:, 2].unsqueeze(0)
+    # torch.sqrt of an fp32 CPU tensor is not correctly rounded; the float64 one rounded to fp32 is (53 >= 2 * 24 + 2 bits: the double
+    # rounding is innocuous for a square root), and that is the number the kernel's IEEE sqrt gives
+    d = torch.sqrt((dx * dx + dy * dy + dz * dz).double()).float()
+    return torch.round(d * torch.tensor(inv_q, dtype=torch.float32, device=a.device)).clamp(max=float(EMD_COST_CAP)).to(torch.int64)
+
+
+def emd_torch(a, b, max_rounds=2_000_000, inv_q=None):
+    """The statement of dgs_emd_auction in PyTorch (CPU or any device; fp32 costs, int64 everything else): a synchronous forward
+    auction with eps-scaling on the integer costs of _emd_costs.
+      phases   eps_0 = max(1, max_cost // 2), then eps <- max(1, eps // 4) until a phase with eps = 1 has run; every phase starts with
+               nobody assigned and keeps the prices, which start at 0
+      round    every unassigned i bids at once against the prices at the start of the round: j1 = the lowest index minimising
+               w = c_ij + p_j (value w1), w2 = the minimum over j != j1, bid = p_j1 + (w2 - w1) + eps; every object that received
+               bids takes the largest packed word bid << 24 | bidder, its price becomes that bid, its former owner is unassigned
+    (the words are kept across rounds: a new bid on an object exceeds its price, which is the last word's bid, so an old word never
+    wins and never equals a new one -- what the kernels do too).  n = 1 is the trivial matching without a round.
+    -> (assignment [n] int64: the object of person i, prices [n] int64, primal, dual, rounds) with
+       primal = sum_i c_{i,assignment(i)} <= OPT + n and dual = sum_i min_j (c_ij + p_j) - sum_j p_j <= OPT.
+    RuntimeError when a round beyond max_rounds would be needed, or a bid does not fit 39 bits."""
+    n = a.shape[0]
+    dev = a.device
+    if inv_q is None:
+        inv_q = _emd_quantum(a, b)[1]
+    cost = _emd_costs(a.float(), b.float(), inv_q)
+    price = torch.zeros(n, dtype=torch.int64, device=dev)
+    if n == 1:
+        c = int(cost[0, 0])
+        return torch.zeros(1, dtype=torch.int64, device=dev), price, c, c, 0
+    index = torch.arange(n, dtype=torch.int64, device=dev)
+    word = torch.zeros(n, dtype=torch.int64, device=dev)
+    big = torch.iinfo(torch.int64).max
+    eps, rounds, phase = max(1, int(cost.max()) // 2), 0, 0
+    while True:
+        owner = torch.full((n,), -1, dtype=torch.int64, device=dev)
+        free = torch.ones(n, dtype=torch.bool, device=dev)
+        bidders = index
+        while bidders.numel():
+            if rounds >= max_rounds:
+                raise RuntimeError("emd: max_rounds = %d reached in phase %d (eps %d) with %d of %d still unassigned"
+                                   % (max_rounds, phase, eps, bidders.numel(), n))
+            w = cost.index_select(0, bidders) + price
+            w1 = w.min(dim=1, keepdim=True).values
+            j1 = torch.where(w == w1, index, n).min(dim=1, keepdim=True).values     # the lowest index among equal w, written out
+            w2 = w.scatter_(1, j1, big).min(dim=1).values
+            j1, w1 = j1.squeeze(1), w1.squeeze(1)
+            bid = price.index_select(0, j1) + (w2 - w1) + eps
+            if int(bid.max()) >= 1 << EMD_BID_BITS:
+                raise RuntimeError("emd: a bid of phase %d does not fit %d bits" % (phase, EMD_BID_BITS))
+            packed = (bid << EMD_BIDDER_BITS) | bidders
+            word.scatter_reduce_(0, j1, packed, "amax", include_self=True)
+            won = torch.nonzero(word.index_select(0, j1) == packed).squeeze(1)      # (index_* calls: the round is op-count bound)
+            wj, wi = j1.index_select(0, won), bidders.index_select(0, won)
+            evicted = owner.index_select(0, wj)
+            price.index_copy_(0, wj, bid.index_select(0, won))
+            owner.index_copy_(0, wj, wi)
+            free.index_fill_(0, wi, False)
+            free.index_fill_(0, torch.masked_select(evicted, evicted >= 0), True)
+            bidders = torch.nonzero(free).squeeze(1)
+            rounds += 1
+        if eps == 1:
+            break
+        eps, phase = max(1, eps // 4), phase + 1
+    assignment = torch.empty(n, dtype=torch.int64, device=dev)
+    assignment[owner] = index
+    primal = int(cost[index, assignment].sum())
+    dual = int((cost + price).min(dim=1).values.sum()) - int(price.sum())
+    return assignment, price, primal, dual, rounds
+
+
+@torch.no_grad()
+def emd(a, b, max_rounds=2_000_000):
+    """Earth mover's distance between two point sets a, b [n,3] of the same size: the mean length of the pairs of a one-to-one
+    matching that is optimal, to a certified gap, for the distances quantised to q = diag / 2^20 (diag: the fp32 bounding-box
+    diagonal of both sets together).  HIP tensors: dgs_emd_auction of libdgs_mesh_ops.so (include/dgs_mesh_ops.h states the cost,
+    the schedule and the field widths); CPU tensors: emd_torch, the same schedule in PyTorch -- the two agree bit for bit.
+      emd          float64 mean of the true Euclidean distances |a_i - b_assignment(i)|: an upper bound on the exact EMD of the
+                   samples, because any matching is
+      emd_gap      (primal - dual) * q / n: the matching is within emd_gap of the optimum of the quantised problem; emd_gap <= q
+      emd_samples  n;   emd_rounds: the auction's rounds;   assignment [n] int64: the object of person i
+    Conventions as in mesh_distance: Euclidean, not squared, mean per point, nothing halved.  Published protocols differ in the
+    number of samples and in normalisation (unit box, unit sphere, squared or halved distances): compare like with like.
+    ValueError: a wrong shape, unequal sizes, no points, non-finite coordinates, mixed devices, n >= 2^24.  RuntimeError: max_rounds
+    reached (the message names the phase, eps and the persons left) -- a partial matching is never returned."""
+    _points(a, "a", "emd"), _points(b, "b", "emd")
+    if a.shape[0] != b.shape[0]:
+        raise ValueError("emd: the two sets must have the same size, not %d and %d" % (a.shape[0], b.shape[0]))
+    n = a.shape[0]
+    if n < 1 or n >= 1 << EMD_BIDDER_BITS:
+        raise ValueError("emd: n must be in [1, 2^24)")
+    if a.device != b.device:
+        raise ValueError("emd: a and b live on different devices")
+    if int(max_rounds) < 1:
+        raise ValueError("emd: max_rounds must be >= 1")
+    a32, b32 = a.float().contiguous(), b.float().contiguous()
+    q, inv_q = _emd_quantum(a32, b32)
+    if a.device.type == "cpu":
+        assignment, _, primal, dual, rounds = emd_torch(a32, b32, int(max_rounds), inv_q)
+    else:
+        from . import _mesh_ops
+        assignment, _, primal, dual, rounds, _ = _mesh_ops.emd_auction(a32, b32, inv_q, int(max_rounds))
+        assignment = assignment.long()
+    d = a32.double() - b32.double()[assignment]
+    length = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]).sqrt()
+    return {"emd": float(length.mean()), "emd_gap": (primal - dual) * q / n, "emd_samples": int(n), "emd_rounds": int(rounds),
+            "assignment": assignment}
+
+
 # ---- sampling -------------------------------------------------------------------------------------------------------------------
 def _mesh_tensors(mesh, device):
     v, f = mesh[0], mesh[1]
@@ -241,7 +375,8 @@ def _surface_hits(points, vertices, faces):
 
 
 @torch.no_grad()
-def mesh_distance(pred, gt, n_samples=100_000, seed=0, thresholds=(0.005, 0.01, 0.02), device="cuda:0", gt_transform=None, mode="samples"):
+def mesh_distance(pred, gt, n_samples=100_000, seed=0, thresholds=(0.005, 0.01, 0.02), device="cuda:0", gt_transform=None, mode="samples",
+                  emd_samples=0):
     """Metrics between the surfaces of pred and gt, each a (vertices [Nv,3], faces [Nf,3]) pair of arrays or tensors.  n_samples
     points are drawn on pred with `seed` and on gt with `seed + 1` (sample_surface), then `nearest` runs both ways on `device`.
     gt_transform: optional [4,4] (column-vector convention, x' = M[:3,:3] x + M[:3,3]) applied to the ground-truth vertices first.
@@ -259,10 +394,16 @@ def mesh_distance(pred, gt, n_samples=100_000, seed=0, thresholds=(0.005, 0.01, 
       normal_consistency  mean |n . n'| of a sample's face normal and its nearest neighbour's (mode "surface": the hit face's,
                           float64), averaged over the two directions
       n_samples, pred_faces, gt_faces, pred_vertices, gt_vertices
+      emd, emd_gap, emd_samples, emd_rounds   only with emd_samples > 0: `emd` of the first emd_samples pred samples against the
+                          first emd_samples gt samples (the samples are independent draws, so a prefix is a uniform sample too); at
+                          most n_samples.  A one-to-one matching: a dense blob near the surface, cheap for the Chamfer distance, is not.
     The per-threshold entries are dicts keyed by '%g' % tau.  Sample-to-sample distances carry the sampling floor: a surface against
     itself measures about 0.5 sqrt(area / n_samples) per direction, not 0; sample-to-surface distances (mode "surface") measure 0."""
     if mode not in ("samples", "surface"):
         raise ValueError("mesh_distance: mode must be 'samples' or 'surface', not %r" % (mode,))
+    emd_samples = int(emd_samples)
+    if emd_samples < 0 or emd_samples > int(n_samples):
+        raise ValueError("mesh_distance: emd_samples must be in [0, n_samples = %d], not %d" % (int(n_samples), emd_samples))
     dev = torch.device(device)
     pv, pf = _mesh_tensors(pred, dev)
     gv, gf = _mesh_tensors(gt, dev)
@@ -292,6 +433,9 @@ def mesh_distance(pred, gt, n_samples=100_000, seed=0, thresholds=(0.005, 0.01, 
     out["normal_consistency"] = 0.5 * (float(nc_p) + float(nc_g))
     out.update(n_samples=int(n_samples), pred_faces=int(pf.shape[0]), gt_faces=int(gf.shape[0]), pred_vertices=int(pv.shape[0]),
                gt_vertices=int(gv.shape[0]))
+    if emd_samples > 0:
+        m = emd(pp[:emd_samples], gp[:emd_samples])
+        out.update({k: m[k] for k in ("emd", "emd_gap", "emd_samples", "emd_rounds")})
     return out
 
 
@@ -324,13 +468,15 @@ def _flat(m):
 
 
 def evaluate_meshes(pred_dir, gt_dir, n_samples=100_000, seed=0, thresholds=(0.005, 0.01, 0.02), device="cuda:0", gt_transform=None, log=None,
-                    mode="samples", clean_gt=False):
+                    mode="samples", clean_gt=False, emd_samples=0):
     """frame_<i>.ply of pred_dir against the i-th ground-truth mesh of gt_dir (its .obj / .ply files in natural sort order), for
     every i.  A different number of frames and ground-truth meshes is an error.  Writes <pred_dir>/mesh_metrics.json:
     {"frames": [{"frame": i, "pred": ..., "gt": ..., <metrics>}], "mean": {<metric>: mean over the frames}, "settings": ...} with
     the per-threshold metrics flattened to 'fscore@0.01', and returns that dict.  mode: as in mesh_distance, recorded under "settings".
     clean_gt: weld and clean every ground-truth mesh on load (mesh_clean.clean_mesh on `device`: an OBJ whose faces each carry their
-    own three vertices becomes an indexed mesh again, duplicated and degenerate triangles go); recorded under "settings" when set."""
+    own three vertices becomes an indexed mesh again, duplicated and degenerate triangles go); recorded under "settings" when set.
+    emd_samples: as in mesh_distance (0: no earth mover's distance, the result is what it was without the argument); the four emd
+    keys then appear per frame and in "mean", and the value is recorded under "settings" when set."""
     def load_gt(path):
         v, f = read_mesh(path)
         if not clean_gt:
@@ -353,7 +499,7 @@ def evaluate_meshes(pred_dir, gt_dir, n_samples=100_000, seed=0, thresholds=(0.0
     rows = []
     for i in range(len(gts)):
         m = _flat(mesh_distance(read_mesh(os.path.join(pred_dir, frames[i])), load_gt(os.path.join(gt_dir, gts[i])), n_samples=n_samples,
-                                seed=seed, thresholds=thresholds, device=device, gt_transform=gt_transform, mode=mode))
+                                seed=seed, thresholds=thresholds, device=device, gt_transform=gt_transform, mode=mode, emd_samples=emd_samples))
         rows.append(dict({"frame": i, "pred": frames[i], "gt": gts[i]}, **m))
         if log is not None:
             log("frame %d (%s vs %s): chamfer %.6f, accuracy %.6f, completeness %.6f, normal consistency %.4f"
@@ -364,6 +510,8 @@ def evaluate_meshes(pred_dir, gt_dir, n_samples=100_000, seed=0, thresholds=(0.0
                            "mode": mode, "gt_transform": None if gt_transform is None else np.asarray(gt_transform, dtype=np.float64).tolist()}}
     if clean_gt:
         result["settings"]["clean_gt"] = True
+    if emd_samples:
+        result["settings"]["emd_samples"] = int(emd_samples)
     with open(os.path.join(pred_dir, "mesh_metrics.json"), "w") as fh:
         json.dump(result, fh, indent=1)
     return result
@@ -382,9 +530,11 @@ def main(argv=None):
     ap.add_argument("--mode", choices=("samples", "surface"), default="samples",
                     help="samples: sample to nearest sample (carries the sampling floor); surface: sample to the other surface, exact")
     ap.add_argument("--clean-gt", action="store_true", help="weld and clean the ground-truth meshes on load (dgs_amd.mesh_clean.clean_mesh)")
+    ap.add_argument("--emd", type=int, default=0, metavar="N",
+                    help="also the earth mover's distance of the first N samples of each mesh (one-to-one matching, dgs_amd.mesh_metrics.emd)")
     a = ap.parse_args(argv)
     return evaluate_meshes(a.pred_dir, a.gt_dir, n_samples=a.samples, seed=a.seed, thresholds=tuple(a.thresholds), device=a.device, log=print,
-                           mode=a.mode, clean_gt=a.clean_gt)
+                           mode=a.mode, clean_gt=a.clean_gt, emd_samples=a.emd)
 
 
 if __name__ == "__main__":

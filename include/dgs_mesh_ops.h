@@ -134,6 +134,46 @@ int dgs_tri_search(long long n_query, const float* query, long long n_tri, const
 /* out = {queries per workgroup, triangles per LDS round, default tri_chunk, floats per table row}. */
 int dgs_tri_layout(int out[4]);
 
+/* Earth mover's distance between two point sets of the same size n: a minimum-cost perfect matching by a synchronous forward
+ * auction with eps-scaling on INTEGER costs (dgs_amd/mesh_metrics.py: emd_torch states the same schedule in
+ * PyTorch and the two agree bit for bit: assignment, prices, rounds).  Version 2 libraries from this commit on also carry the
+ * dgs_emd_* pair; the version number is unchanged because nothing that existed before changes (the precedent of dgs_tri_*).
+ *
+ * COST.  c_ij = min(rint(sqrt((dx * dx + dy * dy) + dz * dz) * inv_q), 2^20) with dx = a_i.x - b_j.x and so on, every operation a
+ * separately rounded fp32 one, the sqrt correctly rounded, rint to nearest even; then an integer in [0, 2^20].  inv_q = 1 / q,
+ * q = diag / 2^20, diag the fp32 bounding-box diagonal of both sets together -- computed by the caller (mesh_metrics._emd_quantum);
+ * inv_q = 0 (diag == 0) makes every cost 0.  Costs are recomputed on the fly: no n x n matrix exists.
+ * SCHEDULE.  Prices p_j start at 0 and are kept across phases.  eps_0 = max(1, max_ij c_ij / 2) (integer division), then
+ * eps <- max(1, eps / 4) until a phase with eps = 1 has run.  A phase starts with nobody assigned.  One ROUND: every unassigned i
+ * bids at once against the prices at the start of the round: w_j = c_ij + p_j, j1 the lowest index that attains w1 = min_j w_j,
+ * w2 = min over j != j1, bid = p_j1 + (w2 - w1) + eps.  Every object that received bids takes the largest packed word
+ * bid << 24 | bidder (a 64-bit atomic maximum: the highest bid and, among equal bids, the highest bidder), its price becomes that
+ * bid and its former owner becomes unassigned.  A phase ends when nobody is unassigned.  The rounds are synchronous and ties are
+ * resolved by the packed words, so the result does not depend on scheduling.  Widths: bidder 24 bits (n < 2^24), bid 39 bits (the word stays below 2^63, like the packed minima above);
+ * prices, bids and w are 64-bit integers throughout; a bid that would not fit 39 bits is detected (status -4), never wrapped.
+ * At the end eps-complementary slackness holds with eps = 1, hence
+ *   primal = sum_i c_{i,assignment(i)} <= OPT + n   and   dual = sum_i min_j (c_ij + p_j) - sum_j p_j <= OPT.
+ *
+ *   a, b [n,3] fp32 (persons, objects);   assignment [n] int32: the object of person i;   prices [n] int64 (both device memory)
+ *   scratch: device memory, 8-byte aligned, at least dgs_emd_layout()[4] + n * dgs_emd_layout()[5] bytes; nothing is allocated here
+ *   result [8] int64 in HOST memory: primal, dual, rounds, max cost, phases, last eps, and on status -3 the phase [4], its eps [5]
+ *     and the persons still unassigned [6]
+ * The host drives the rounds: two launches per round (bid, resolve), enqueued in batches; the unassigned count is read once per
+ * batch (this call synchronises `stream`).  No kernel waits for another workgroup.  Rounds enqueued after a phase has converged
+ * change nothing, and `rounds` counts only rounds that had bidders -- the count of the statement.
+ * max_rounds caps the rounds over all phases: when a round would exceed it the call returns -3 with the phase, eps and bidders left
+ * in the message; a partial matching is never returned as a result (assignment is then unspecified), and the same buffers may be
+ * used for another call.  n == 0 and n == 1 launch nothing (n == 1: the trivial matching, the cost computed on the host).
+ * Refused with a negative status before any launch: a null pointer with n > 0 (scratch with n > 1), n < 0, n >= 2^24,
+ * max_rounds <= 0, inv_q negative or not finite, a scratch buffer too small or misaligned.  No address can leave an array: every
+ * index is a person or an object below n (list entries are written from [0, n) only, a list holds at most n of them). */
+int dgs_emd_auction(long long n, const float* a, const float* b, float inv_q, long long max_rounds, void* scratch,
+                    long long scratch_bytes, int* assignment, long long* prices, long long* result, void* stream);
+
+/* out = {threads per workgroup, objects per LDS round of the dense bidding kernel, the bidder count up to which the sparse bidding
+ *        kernel (a workgroup per bidder) runs, entries of `result`, fixed bytes of scratch, bytes of scratch per point}. */
+int dgs_emd_layout(int out[6]);
+
 /* Z-buffer rasterizer of a triangle mesh: which face is nearest at every pixel centre, its depth, its barycentrics and the
  * perspective-correct interpolation of per-vertex attributes -- the images of dgs_amd/mesh_render.py (the role nvdiffrast has in
  * the reference's render_mesh.py:221-240).  Not differentiable.  Version 2 libraries from this commit on also carry the
