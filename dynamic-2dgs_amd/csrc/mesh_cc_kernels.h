@@ -1,4 +1,5 @@
-// mesh_cc_kernels.h -- the connected components of the mesh clean-up (mesh_ops.hip: dgs_cc_labels).
+// mesh_cc_kernels.h -- the connected components of the mesh clean-up (mesh_ops.hip: dgs_cc_labels) and, after them, the quadric
+// vertex clustering of the mesh simplification (dgs_simplify_accumulate, dgs_simplify_solve).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -59,6 +60,187 @@ __global__ __launch_bounds__(CC_THREADS) void cc_compress_kernel(long long n_nod
         if (p == (int)i) continue;
         const int r = cc_find(label, p);
         if (r != p) __hip_atomic_store(label + i, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// ---- quadric vertex clustering (mesh_ops.hip: dgs_simplify_accumulate, dgs_simplify_solve) ---------------------------------------
+// include/dgs_mesh_ops.h states the arithmetic; every sum is an exact int64 addition, so the grouping below cannot change a bit.
+// A row of a cluster is 16 int64 = 128 contiguous bytes: column 0 count, 1..3 position, 4..6 colour, 7..12 A (xx xy xz yy yz zz),
+// 13..15 b.  The vertex kernel adds columns 0..6, the face kernel columns 7..15.
+// COMBINING ON CHIP.  A naive scatter is one 8-byte atomic per lane and column, 64 lanes in up to 64 rows: the slowest shape there
+// is.  Marching tetrahedra emits vertices and faces in cell order, so neighbouring items mostly share a cluster.  A workgroup
+// therefore (1) stores key and values of its 256 items in LDS, (2) finds the runs of equal neighbouring keys (a head is an item whose
+// left neighbour has another key; ballot + popcount number the heads, a 4-entry table joins the waves), (3) gives every run to 16
+// lanes, one per column, each of which sums its column over the run out of LDS and issues ONE atomic: a wave instruction covers
+// four runs, each lane group a contiguous piece (56 / 72 bytes) of one row.  Zero sums (a mesh without colours) are not sent.
+// Items past the end and ids outside their range carry the key -1: they take part in every barrier and are skipped at the atomic,
+// which is the index guard -- no address is formed from such an id.
+constexpr int SIMP_THREADS = 256, SIMP_ITEMS_PER_THREAD = 1, SIMP_ROW = 16, SIMP_Q = 24, SIMP_W_MAX = 16, SIMP_LAMBDA_EXP = -10;
+constexpr int SIMP_POS_BITS = 30, SIMP_COL_BITS = 24, SIMP_WAVES = SIMP_THREADS / 64;
+
+template <int NCOL>
+struct SimpShared {
+    long long val[SIMP_THREADS][NCOL];
+    int key[SIMP_THREADS];
+    int start[SIMP_THREADS + 1];       // first item of every run, then SIMP_THREADS
+    int wave_runs[SIMP_WAVES];
+};
+
+// Every thread of the workgroup calls this (no early exit before it).  COL0: the first of the NCOL columns these values go to.
+template <int NCOL, int COL0>
+__device__ __forceinline__ void simp_combine(SimpShared<NCOL>& sh, int key, const long long (&v)[NCOL], long long n_clusters,
+                                             long long* __restrict__ rows) {
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    sh.key[t] = key;
+#pragma unroll
+    for (int c = 0; c < NCOL; ++c) sh.val[t][c] = v[c];
+    __syncthreads();
+    const bool head = t == 0 || sh.key[t - 1] != key;
+    const unsigned long long heads = __ballot(head);
+    if (lane == 0) sh.wave_runs[wave] = __popcll(heads);
+    __syncthreads();
+    int base = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < SIMP_WAVES; ++w) {
+        const int n = sh.wave_runs[w];
+        base += w < wave ? n : 0;
+        total += n;
+    }
+    if (head) sh.start[base + __popcll(heads & ((1ull << lane) - 1ull))] = t;
+    if (t == 0) sh.start[total] = SIMP_THREADS;
+    __syncthreads();
+    const int col = t & (SIMP_ROW - 1);
+    for (int r = t / SIMP_ROW; r < total; r += SIMP_THREADS / SIMP_ROW) {
+        const int s = sh.start[r], e = sh.start[r + 1], k = sh.key[s];
+        if (col >= NCOL || k < 0 || k >= n_clusters) continue;          // index guard: rows[k] exists
+        long long sum = 0;
+        for (int i = s; i < e; ++i) sum += sh.val[i][col];
+        if (sum != 0) atomicAdd((unsigned long long*)(rows + (long long)k * SIMP_ROW + COL0 + col), (unsigned long long)sum);
+    }
+    __syncthreads();                                                    // the buffers are free for the next call
+}
+
+__device__ __forceinline__ long long simp_fixed(float x, float scale) { return (long long)rintf(x * scale); }   // scale = 2^k: the product is exact
+
+__global__ __launch_bounds__(SIMP_THREADS) void simp_vertex_kernel(long long n_vertices, const float* __restrict__ vertices,
+                                                                   const float* __restrict__ colors, const int* __restrict__ cluster,
+                                                                   long long n_clusters, const float* __restrict__ centres, float cell,
+                                                                   long long* __restrict__ rows) {
+    __shared__ SimpShared<7> sh;
+    const long long i = (long long)blockIdx.x * SIMP_THREADS + threadIdx.x;
+    int key = -1;
+    long long v[7] = {0, 0, 0, 0, 0, 0, 0};
+    if (i < n_vertices) {
+        const int k = cluster[i];
+        if (k >= 0 && k < n_clusters) {
+            key = k;
+            v[0] = 1;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) v[1 + a] = simp_fixed((vertices[3 * i + a] - centres[3 * (long long)k + a]) / cell, (float)(1 << SIMP_POS_BITS));
+            if (colors) {
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    const float c = colors[3 * i + a];
+                    v[4 + a] = simp_fixed(c > 0.0f ? (c < 1.0f ? c : 1.0f) : 0.0f, (float)(1 << SIMP_COL_BITS));   // NaN counts as 0
+                }
+            }
+        }
+    }
+    simp_combine<7, 0>(sh, key, v, n_clusters, rows);
+}
+
+__global__ __launch_bounds__(SIMP_THREADS) void simp_face_kernel(long long n_faces, const int* __restrict__ faces, long long n_vertices,
+                                                                 const float* __restrict__ vertices, const int* __restrict__ cluster,
+                                                                 long long n_clusters, const float* __restrict__ centres, float cell,
+                                                                 long long* __restrict__ rows) {
+    __shared__ SimpShared<9> sh;
+    const long long i = (long long)blockIdx.x * SIMP_THREADS + threadIdx.x;
+    bool ok = false;
+    int k[3] = {-1, -1, -1};
+    float p[3][3], nh[3] = {0.0f, 0.0f, 0.0f}, w = 0.0f;
+    if (i < n_faces) {
+        const int f0 = faces[3 * i], f1 = faces[3 * i + 1], f2 = faces[3 * i + 2];
+        if (f0 >= 0 && f0 < n_vertices && f1 >= 0 && f1 < n_vertices && f2 >= 0 && f2 < n_vertices) {   // index guard
+            const int f[3] = {f0, f1, f2};
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                k[c] = cluster[f[c]];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) p[c][a] = vertices[3 * (long long)f[c] + a];
+            }
+            const float ux = p[1][0] - p[0][0], uy = p[1][1] - p[0][1], uz = p[1][2] - p[0][2];
+            const float vx = p[2][0] - p[0][0], vy = p[2][1] - p[0][1], vz = p[2][2] - p[0][2];
+            const float nx = uy * vz - uz * vy, ny = uz * vx - ux * vz, nz = ux * vy - uy * vx;
+            // the length through the fp64 square root, which is correctly rounded on both sides (sqrtf is not on the device)
+            const float l = (float)sqrt((double)((nx * nx + ny * ny) + nz * nz));
+            if (l > 0.0f && l < INFINITY) {                             // a face with area; NaN fails both
+                ok = true;
+                nh[0] = nx / l, nh[1] = ny / l, nh[2] = nz / l;
+                w = fminf((0.5f * l) / (cell * cell), (float)SIMP_W_MAX);
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {                                       // corner c speaks for its cluster if no earlier corner is in it
+        const bool first = c == 0 || (k[c] != k[0] && (c == 1 || k[c] != k[1]));
+        const bool mine = ok && first && k[c] >= 0 && k[c] < n_clusters;
+        if (!__syncthreads_or(mine)) continue;                          // (uniform: the whole workgroup skips the slot)
+        long long v[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (mine) {
+            const long long m = (k[0] == k[c]) + (k[1] == k[c]) + (k[2] == k[c]);
+            const float* ctr = centres + 3 * (long long)k[c];
+            const float qx = (p[c][0] - ctr[0]) / cell, qy = (p[c][1] - ctr[1]) / cell, qz = (p[c][2] - ctr[2]) / cell;
+            const float d = -((nh[0] * qx + nh[1] * qy) + nh[2] * qz);
+            const float scale = (float)(1 << SIMP_Q), wd = w * d;
+            int o = 0;
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+#pragma unroll
+                for (int b = a; b < 3; ++b) v[o++] = m * simp_fixed((w * nh[a]) * nh[b], scale);
+#pragma unroll
+            for (int a = 0; a < 3; ++a) v[6 + a] = m * simp_fixed(wd * nh[a], scale);
+        }
+        simp_combine<9, 7>(sh, mine ? k[c] : -1, v, n_clusters, rows);
+    }
+}
+
+// One thread per cluster: the fp64 solve of include/dgs_mesh_ops.h, operation by operation.
+__global__ __launch_bounds__(SIMP_THREADS) void simp_solve_kernel(long long n_clusters, const long long* __restrict__ rows,
+                                                                  const float* __restrict__ centres, float cell, int placement,
+                                                                  float* __restrict__ vertices, float* __restrict__ colors) {
+    const long long i = (long long)blockIdx.x * SIMP_THREADS + threadIdx.x;
+    if (i >= n_clusters) return;
+    const long long* r = rows + i * SIMP_ROW;
+    const double count = (double)r[0];
+    const double pden = count * (double)(1 << SIMP_POS_BITS), cden = count * (double)(1 << SIMP_COL_BITS);
+    double xb[3], x[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double q = (double)r[1 + a] / pden;                       // count 0 (a cluster no vertex names): NaN fails both tests -> 0
+        xb[a] = q > -1.0 ? (q < 1.0 ? q : 1.0) : -1.0;
+        if (!(q == q)) xb[a] = 0.0;
+        x[a] = xb[a];
+    }
+    if (placement == 1) {
+        const double a00 = (double)r[7], a01 = (double)r[8], a02 = (double)r[9], a11 = (double)r[10], a12 = (double)r[11], a22 = (double)r[12];
+        const double t = (a00 + a11) + a22, reg = t * 0x1p-10;
+        static_assert(SIMP_LAMBDA_EXP == -10, "reg above is t * 2^SIMP_LAMBDA_EXP");
+        const double m00 = a00 + reg, m11 = a11 + reg, m22 = a22 + reg;
+        const double r0 = reg * xb[0] - (double)r[13], r1 = reg * xb[1] - (double)r[14], r2 = reg * xb[2] - (double)r[15];
+        const double c00 = m11 * m22 - a12 * a12, c01 = a02 * a12 - a01 * m22, c02 = a01 * a12 - a02 * m11;
+        const double c11 = m00 * m22 - a02 * a02, c12 = a01 * a02 - m00 * a12, c22 = m00 * m11 - a01 * a01;
+        const double det = (m00 * c00 + a01 * c01) + a02 * c02;
+        if (t > 0.0 && det > 0.0 && det < (double)INFINITY) {
+            const double y0 = ((c00 * r0 + c01 * r1) + c02 * r2) / det;
+            const double y1 = ((c01 * r0 + c11 * r1) + c12 * r2) / det;
+            const double y2 = ((c02 * r0 + c12 * r1) + c22 * r2) / det;
+            if (fabs(y0) <= 1.0 && fabs(y1) <= 1.0 && fabs(y2) <= 1.0) x[0] = y0, x[1] = y1, x[2] = y2;   // NaN fails
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        vertices[3 * i + a] = centres[3 * i + a] + (float)x[a] * cell;
+        if (colors) colors[3 * i + a] = count > 0.0 ? (float)((double)r[4 + a] / cden) : 0.0f;
     }
 }
 

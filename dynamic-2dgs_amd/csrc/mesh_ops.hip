@@ -1,6 +1,7 @@
 // libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion of rendered depth maps, marching tetrahedra, the all-pairs
 // nearest-neighbour and closest-triangle searches and the earth mover's distance (an auction solver) of the mesh metrics, the
-// z-buffer triangle rasterizer of the mesh images and the connected components of the mesh clean-up, gfx950.
+// z-buffer triangle rasterizer of the mesh images, the connected components of the mesh clean-up and the quadric vertex
+// clustering of the mesh simplification, gfx950.
 // Compiled with -ffp-contract=off: every fp32 operation of the kernels rounds on its own, which is what makes the result equal to
 // the PyTorch statement of the same arithmetic (dgs_amd/mesh.py) instead of close to it.
 // The kernels live in one header per family, included in the order they were written; this file is the C ABI: the argument checks
@@ -320,5 +321,48 @@ int dgs_cc_labels(long long n_nodes, const int* groups, long long n_groups, int 
 }
 
 int dgs_cc_layout(int out[2]) { return layout("dgs_cc_layout", out, {CC_THREADS, CC_GROUPS_PER_THREAD}); }
+
+int dgs_simplify_accumulate(long long n_vertices, const float* vertices, const float* colors, long long n_faces, const int* faces,
+                            const int* cluster, long long n_clusters, const float* centres, float cell, long long* rows, void* stream) {
+    if (n_vertices < 0 || n_faces < 0 || n_clusters < 0) return fail(-1, "dgs_simplify_accumulate: negative count");
+    if (n_vertices >= (1LL << 31) || n_faces >= (1LL << 31) || n_clusters >= (1LL << 31))
+        return fail(-1, "dgs_simplify_accumulate: every count must be below 2^31 (ids are int32, and the sums are sized for it)");
+    if (!(cell > 0.0f) || !std::isfinite(cell)) return fail(-1, "dgs_simplify_accumulate: cell must be positive and finite");
+    if ((n_clusters > 0 && (!rows || !centres)) || (n_vertices > 0 && (!vertices || !cluster)) || (n_faces > 0 && (!faces || !vertices || !cluster)))
+        return fail(-1, "dgs_simplify_accumulate: null pointer");
+    if (n_clusters == 0) return 0;
+    hipError_t e = hipMemsetAsync(rows, 0, (size_t)n_clusters * SIMP_ROW * sizeof(long long), (hipStream_t)stream);
+    if (e != hipSuccess) return fail(-2, std::string("dgs_simplify_accumulate (clear): ") + hipGetErrorString(e));
+    const long long per_block = (long long)SIMP_THREADS * SIMP_ITEMS_PER_THREAD;
+    auto blocks = [&](long long n) { return dim3((unsigned)((n + per_block - 1) / per_block)); };       // n < 2^31: below 2^23 workgroups
+    if (n_vertices > 0) {
+        hipLaunchKernelGGL(simp_vertex_kernel, blocks(n_vertices), dim3(SIMP_THREADS), 0, (hipStream_t)stream, n_vertices, vertices, colors, cluster,
+                           n_clusters, centres, cell, rows);
+        if (int rc = launched("dgs_simplify_accumulate (vertices)")) return rc;
+    }
+    if (n_faces > 0 && n_vertices > 0) {
+        hipLaunchKernelGGL(simp_face_kernel, blocks(n_faces), dim3(SIMP_THREADS), 0, (hipStream_t)stream, n_faces, faces, n_vertices, vertices, cluster,
+                           n_clusters, centres, cell, rows);
+        if (int rc = launched("dgs_simplify_accumulate (faces)")) return rc;
+    }
+    return 0;
+}
+
+int dgs_simplify_solve(long long n_clusters, const long long* rows, const float* centres, float cell, int placement, float* vertices,
+                       float* colors, void* stream) {
+    if (n_clusters < 0) return fail(-1, "dgs_simplify_solve: negative count");
+    if (n_clusters >= (1LL << 31)) return fail(-1, "dgs_simplify_solve: n_clusters must be below 2^31");
+    if (placement != 0 && placement != 1) return fail(-1, "dgs_simplify_solve: placement must be 0 (average) or 1 (quadric)");
+    if (!(cell > 0.0f) || !std::isfinite(cell)) return fail(-1, "dgs_simplify_solve: cell must be positive and finite");
+    if (n_clusters > 0 && (!rows || !centres || !vertices)) return fail(-1, "dgs_simplify_solve: null pointer");
+    if (n_clusters == 0) return 0;
+    hipLaunchKernelGGL(simp_solve_kernel, dim3((unsigned)((n_clusters + SIMP_THREADS - 1) / SIMP_THREADS)), dim3(SIMP_THREADS), 0, (hipStream_t)stream,
+                       n_clusters, rows, centres, cell, placement, vertices, colors);
+    return launched("dgs_simplify_solve");
+}
+
+int dgs_simplify_layout(int out[5]) {
+    return layout("dgs_simplify_layout", out, {SIMP_THREADS, SIMP_ITEMS_PER_THREAD, SIMP_Q, SIMP_W_MAX, SIMP_LAMBDA_EXP});
+}
 
 }  // extern "C"

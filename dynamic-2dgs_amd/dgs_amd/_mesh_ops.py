@@ -1,6 +1,7 @@
 """ctypes binding of libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion, marching tetrahedra, the all-pairs nearest-neighbour
-and closest-triangle searches, the auction solver of the earth mover's distance, the z-buffer triangle rasterizer and the connected components for gfx950, used by dgs_amd.mesh,
-dgs_amd.mesh_metrics, dgs_amd.mesh_render and dgs_amd.mesh_clean when the data lives on a HIP device.  CPU tensors use the PyTorch /
+and closest-triangle searches, the auction solver of the earth mover's distance, the z-buffer triangle rasterizer, the connected components and the
+quadric vertex clustering for gfx950, used by dgs_amd.mesh, dgs_amd.mesh_metrics, dgs_amd.mesh_render, dgs_amd.mesh_clean and
+dgs_amd.mesh_simplify when the data lives on a HIP device.  CPU tensors use the PyTorch /
 NumPy statements in those modules."""
 import ctypes
 import os
@@ -41,6 +42,10 @@ _SIGNATURES = {
     # connected components
     "dgs_cc_labels": (_ci, [_ll, _vp, _ll, _ci, _vp, _vp]),
     "dgs_cc_layout": (_ci, _LAYOUT),
+    # quadric vertex clustering (its kernels close mesh_cc_kernels.h)
+    "dgs_simplify_accumulate": (_ci, [_ll, _vp, _vp, _ll, _vp, _vp, _ll, _vp, _cf, _vp, _vp]),
+    "dgs_simplify_solve": (_ci, [_ll, _vp, _vp, _cf, _ci, _vp, _vp, _vp]),
+    "dgs_simplify_layout": (_ci, _LAYOUT),
 }
 _SOURCES = ["mesh_ops.hip", "mesh_common.h", "mesh_fusion_kernels.h", "mesh_search_kernels.h", "mesh_raster_kernels.h", "mesh_cc_kernels.h"]
 _LIB = _dgs_build.NativeLibrary(
@@ -295,3 +300,49 @@ def cc_labels(groups, n_nodes):
                                label.data_ptr() if n_nodes else None, _stream(dev))
     _check(lib, rc, "dgs_cc_labels")
     return label
+
+
+def simplify_layout():
+    """(threads per workgroup, items per thread, Q, W_MAX, exponent of lambda) of dgs_simplify_accumulate / dgs_simplify_solve."""
+    return _layout("dgs_simplify_layout", 5)
+
+
+def simplify_accumulate(vertices, colors, faces, cluster, centres, cell):
+    """dgs_simplify_accumulate -> rows [C,16] int64 on the device of vertices [V,3]: colors [V,3] or None, faces [F,3] int32, cluster
+    [V] int32 (the cell of every vertex), centres [C,3], cell a float."""
+    lib = load()
+    dev = vertices.device
+    _f32(vertices, "vertices"), _f32(centres, "centres")
+    if colors is not None:
+        _f32(colors, "colors")
+    for t, what in ((faces, "faces"), (cluster, "cluster")):
+        if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+            raise RuntimeError("simplify_accumulate: %s must be a contiguous int32 HIP tensor" % what)
+    V, F, C = vertices.shape[0], faces.shape[0], centres.shape[0]
+    if vertices.shape != (V, 3) or faces.shape != (F, 3) or cluster.shape != (V,) or centres.shape != (C, 3) or (colors is not None and colors.shape != (V, 3)):
+        raise RuntimeError("simplify_accumulate: vertices [V,3], colors [V,3], faces [F,3], cluster [V] and centres [C,3] are expected")
+    if any(t is not None and t.device != dev for t in (colors, faces, cluster, centres)):
+        raise RuntimeError("simplify_accumulate: every tensor must live on the device of vertices")
+    rows = torch.empty((C, 16), dtype=torch.int64, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    with torch.cuda.device(dev):
+        rc = lib.dgs_simplify_accumulate(V, ptr(vertices), ptr(colors), F, ptr(faces), ptr(cluster), C, ptr(centres), float(cell), ptr(rows), _stream(dev))
+    _check(lib, rc, "dgs_simplify_accumulate")
+    return rows
+
+
+def simplify_solve(rows, centres, cell, quadric=True, with_colors=False):
+    """dgs_simplify_solve -> (vertices [C,3] f32, colors [C,3] f32 or None) from the rows of simplify_accumulate."""
+    lib = load()
+    dev = rows.device
+    _f32(centres, "centres")
+    C = centres.shape[0]
+    if not (rows.is_cuda and rows.dtype == torch.int64 and rows.is_contiguous() and rows.shape == (C, 16)) or centres.shape != (C, 3) or centres.device != dev:
+        raise RuntimeError("simplify_solve: rows [C,16] int64 and centres [C,3] fp32 on one HIP device are expected")
+    vertices = torch.empty((C, 3), dtype=torch.float32, device=dev)
+    colors = torch.empty((C, 3), dtype=torch.float32, device=dev) if with_colors else None
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    with torch.cuda.device(dev):
+        rc = lib.dgs_simplify_solve(C, ptr(rows), ptr(centres), float(cell), 1 if quadric else 0, ptr(vertices), ptr(colors), _stream(dev))
+    _check(lib, rc, "dgs_simplify_solve")
+    return vertices, colors

@@ -6,6 +6,7 @@ open3d / trimesh.
                                   render_mesh_trajectory.py:41-88 are built on it): a cluster per triangle, triangles and area per cluster
   filter_components            <- utils/mesh_utils.py:24-45 post_process_mesh: mesh.keep_largest_components with every step on the device
   clean_mesh                   <- render_mesh_trajectory.py:41-88 clean_mesh, without its fill_holes (trimesh's; not built)
+(Simplification -- open3d's simplify_vertex_clustering -- is dgs_amd.mesh_simplify; it shares the face steps of clean_mesh.)
 
 On a HIP device the components are the union-find kernels of libdgs_mesh_ops.so (dgs_cc_labels, include/dgs_mesh_ops.h); on CPU
 tensors component_labels runs a PyTorch label propagation.  The label of a node is the smallest node id of its component, which is
@@ -170,6 +171,23 @@ def _compact(vertices, faces, colors, keep_face):
     return vertices[used], f, None if colors is None else colors[used]
 
 
+def _first_proper_faces(f):
+    """[F] bool for faces f [F,3] int64: steps (b) and (c) of clean_mesh (simplify_mesh applies them to the cluster ids) -- true for
+    a face that names three different vertices and repeats no earlier face up to a rotation of its corners."""
+    F, dev = f.shape[0], f.device
+    keep = torch.ones(F, dtype=torch.bool, device=dev)
+    if F:
+        # (b): rotate the smallest corner to the front; rows that are equal then are rotations of each other
+        shift = f.argmin(1, keepdim=True)
+        canon = torch.gather(f, 1, (shift + torch.arange(3, device=dev)) % 3)
+        _, inverse = torch.unique(canon, dim=0, return_inverse=True)
+        ids = torch.arange(F, dtype=torch.int64, device=dev)
+        first = torch.full((F,), F, dtype=torch.int64, device=dev).scatter_reduce_(0, inverse, ids, "amin")
+        keep = first[inverse] == ids
+        keep &= (f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 2] != f[:, 0])          # (c)
+    return keep
+
+
 @torch.no_grad()
 def filter_components(vertices, faces, colors=None, n_keep=1000, min_faces=50, adjacency="vertex"):
     """The rule of mesh.keep_largest_components -- keep the components that have at least as many faces as the n_keep-th largest
@@ -215,17 +233,7 @@ def clean_mesh(vertices, faces, colors=None, min_triangles_connected=-1, adjacen
         ids = torch.arange(V, dtype=torch.int64, device=dev)
         first = torch.full((V,), V, dtype=torch.int64, device=dev).scatter_reduce_(0, inverse, ids, "amin")
         f = first[inverse][f]                                 # every corner named by the first vertex at its position
-    keep = torch.ones(F, dtype=torch.bool, device=dev)
-    if F:
-        # (b): rotate the smallest corner to the front; rows that are equal then are rotations of each other
-        shift = f.argmin(1, keepdim=True)
-        canon = torch.gather(f, 1, (shift + torch.arange(3, device=dev)) % 3)
-        _, inverse = torch.unique(canon, dim=0, return_inverse=True)
-        ids = torch.arange(F, dtype=torch.int64, device=dev)
-        first = torch.full((F,), F, dtype=torch.int64, device=dev).scatter_reduce_(0, inverse, ids, "amin")
-        keep = first[inverse] == ids
-        keep &= (f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 2] != f[:, 0])          # (c)
-    f = f[keep]
+    f = f[_first_proper_faces(f)]                             # (b), (c)
     if min_triangles_connected > 0 and f.shape[0]:            # (d)
         label = _face_labels(V, f, adjacency)
         counts = _label_counts(label, V if adjacency == "vertex" else f.shape[0])[0]

@@ -1,8 +1,8 @@
 /*
  * dgs_mesh_ops.h -- C ABI of the mesh kernels: depth-map fusion into a truncated signed distance volume, marching tetrahedra over
  * it, the all-pairs nearest-neighbour and closest-triangle searches behind the geometry metrics of dgs_amd/mesh_metrics.py, the
- * z-buffer triangle rasterizer behind the mesh images of dgs_amd/mesh_render.py, and the connected components behind
- * dgs_amd/mesh_clean.py.  The first two replace the PyTorch / open3d path of the reference's render_mesh.py:
+ * z-buffer triangle rasterizer behind the mesh images of dgs_amd/mesh_render.py, the connected components behind
+ * dgs_amd/mesh_clean.py, and the quadric vertex clustering behind dgs_amd/mesh_simplify.py.  The first two replace the PyTorch / open3d path of the reference's render_mesh.py:
  *
  *   dgs_tsdf_integrate          <-  utils/mesh_utils.py:218-266  compute_sdf_perframe + compute_unbounded_tsdf (inv_contraction=None)
  *   dgs_mt_classify / _emit     <-  utils/mesh_utils.py:158-199 / :268-271  volume.extract_triangle_mesh() / marching_cubes_with_contraction
@@ -283,6 +283,75 @@ int dgs_cc_labels(long long n_nodes, const int* groups, long long n_groups, int 
 /* out = {threads per workgroup, groups per thread}: a workgroup takes out[0] * out[1] groups -- the sizes at which the code changes
  * path (a second workgroup, a ragged last one). */
 int dgs_cc_layout(int out[2]);
+
+/* Mesh simplification by vertex clustering with quadric placement: the kernels behind dgs_amd/mesh_simplify.py (open3d's
+ * simplify_vertex_clustering(contraction=Quadric / Average), which the reference's users reach for before printing a mesh).
+ * Version 2 libraries from this commit on also carry the dgs_simplify_* triple; the version number is unchanged because nothing
+ * that existed before changes.  THE STATEMENT -- every fp operation rounded on its own, fp32 unless it says fp64; rn() is
+ * round-to-nearest-even to an integer; dgs_amd/mesh_simplify.py states the same arithmetic in PyTorch and CPU tensors run it:
+ *
+ * 1. CELLS (the wrapper: PyTorch on the tensors' device).  origin defaults to the per-axis minimum of the vertices - cell / 2;
+ *    ijk = floor((v - origin) / cell), each component in [0, 2^21); the cluster id of a vertex is the rank of its (i, j, k) among
+ *    the occupied cells in ascending lexicographic order; centre = origin + (ijk + 0.5) * cell.
+ * 2. SUMS (dgs_simplify_accumulate).  rows [n_clusters,16] int64, one row per cluster:
+ *      column 0        the number of vertices of the cluster
+ *      columns 1..3    sum over its vertices of rn(((v - centre) / cell) * 2^30), per axis
+ *      columns 4..6    sum over its vertices of rn(clamp(colour, 0, 1) * 2^24), a NaN colour counting as 0 (0 without colours)
+ *      columns 7..12   A: xx xy xz yy yz zz;   columns 13..15   b
+ *    Per face (a, b, c): n = (b - a) x (c - a), each component a difference of two rounded products (n.x = e1.y e2.z - e1.z e2.y
+ *    ...); l = fp32(sqrt(fp64((n.x n.x + n.y n.y) + n.z n.z))) -- the fp64 square root, because it is correctly rounded on the
+ *    device and on the host while the device's fp32 one is not.  A face counts iff 0 < l < inf.  nh = n / l per component;
+ *    w = min((0.5 l) / (cell cell), W_MAX).  For every distinct cluster k among the three corners, with m the number of corners in
+ *    k and p the first of them: u = (p - centre_k) / cell;  d = -((nh.x u.x + nh.y u.y) + nh.z u.z);  the row of k receives
+ *    m * rn(((w nh_i) nh_j) * 2^Q) for i <= j and m * rn(((w d) nh_i) * 2^Q).  All sums are integer additions: their order and
+ *    grouping cannot change a bit, which is what lets the kernel combine neighbouring lanes on chip and still be equal to the
+ *    PyTorch statement.
+ *    Q = 24, W_MAX = 16 (a face of 16 cell areas; larger faces are weighted as that).  NO SUM CAN OVERFLOW for any mesh the library
+ *    accepts (fewer than 2^31 vertices and fewer than 2^31 faces, hence fewer than 3 * 2^31 corner incidences in one cell):
+ *      - count < 2^31.
+ *      - |u| < 2 per axis: the vertex lies in its cell up to the rounding of steps 1 (ijk < 2^21 and 24-bit significands put
+ *        (v - origin) / cell and the centre each within 2^21 * 2^-23 = 1/4 cell of their exact values), so |u| <= 1/2 + 1/4 + 1/4
+ *        and a rounding; a position term is below 2^31, a sum below 2^62.
+ *      - a colour term is at most 2^24, a sum below 2^55.
+ *      - |nh_i| <= 1 + 2^-22, so |w nh_i nh_j| < 1.001 W_MAX and a term of A is below 1.001 * 2^28 + 1/2; |d| <= |nh| |u| <
+ *        1.001 * 2 sqrt(3) < 3.5, so a term of b is below 3.5 * 2^28 + 1/2; 3 * 2^31 of them stay below 10.5 * 2^59 + 2^32 < 2^63.
+ * 3. SOLVE (dgs_simplify_solve), per cluster in fp64.  An int64 is converted to fp64 by one rounding.  The sums enter as they are:
+ *    the solution does not change when A and b are scaled together, so 2^-Q is never applied.
+ *      xb_i = clamp(pos_i / (count * 2^30), -1, 1)                          (0 where count = 0)
+ *      placement 0 (average): x = xb.   placement 1 (quadric):
+ *      t = (a00 + a11) + a22;  g = t * 2^-10;  m00 = a00 + g, m11 = a11 + g, m22 = a22 + g;  r_i = g * xb_i - b_i
+ *      c00 = m11 m22 - a12 a12   c01 = a02 a12 - a01 m22   c02 = a01 a12 - a02 m11
+ *      c11 = m00 m22 - a02 a02   c12 = a01 a02 - m00 a12   c22 = m00 m11 - a01 a01
+ *      det = (m00 c00 + a01 c01) + a02 c02
+ *      x0 = ((c00 r0 + c01 r1) + c02 r2) / det,  x1 = ((c01 r0 + c11 r1) + c12 r2) / det,  x2 = ((c02 r0 + c12 r1) + c22 r2) / det
+ *      x = xb unless t > 0, 0 < det < inf and every |x_i| <= 1 (a NaN fails).
+ *    That is (A + lambda t I) x = -b + lambda t xb with lambda = 2^-10: the minimiser of the summed squared plane distances, pulled
+ *    to the cluster mean along the directions the planes leave free (flat and creased regions, where A has rank 1 or 2).
+ *    vertex = centre + fp32(x) * cell (fp32);  colour = fp32(col_i / (count * 2^24)).  Every output vertex lies within one cell of
+ *    its cell centre per axis.
+ * 4. FACES (the wrapper: PyTorch): every index replaced by its cluster; faces that name a cluster twice and later repeats of a face
+ *    up to rotation dropped; unreferenced vertices dropped; order and winding kept.
+ *
+ * dgs_simplify_accumulate: vertices [n_vertices,3], colors [n_vertices,3] or null, faces [n_faces,3] int32, cluster [n_vertices]
+ * int32, centres [n_clusters,3], rows [n_clusters,16] int64 (cleared by the call).  Up to three operations on `stream`: the clear,
+ * a launch over the vertices, a launch over the faces.  A workgroup keeps its items' keys and values in LDS, finds the runs of
+ * neighbouring items with one cluster, and sums every run on chip; a run then costs one 64-bit atomic per non-zero column, 16 lanes
+ * on the 128 contiguous bytes of one row (csrc/mesh_cc_kernels.h).  A vertex id outside [0, n_vertices) drops its face, a cluster
+ * id outside [0, n_clusters) drops that vertex or that corner's contribution: index guards, so no address leaves a buffer; the
+ * Python wrapper produces no such ids.
+ * Refused with a negative status before any launch: a negative count, a count >= 2^31, cell not positive and finite, a null pointer
+ * with a non-zero count, a placement outside {0, 1}.  n_clusters == 0 returns 0 and launches nothing; a zero n_vertices or n_faces
+ * skips that launch. */
+int dgs_simplify_accumulate(long long n_vertices, const float* vertices, const float* colors, long long n_faces, const int* faces,
+                            const int* cluster, long long n_clusters, const float* centres, float cell, long long* rows, void* stream);
+
+/* rows, centres as above -> vertices [n_clusters,3] and, unless null, colors [n_clusters,3].  One launch, a thread per cluster. */
+int dgs_simplify_solve(long long n_clusters, const long long* rows, const float* centres, float cell, int placement, float* vertices,
+                       float* colors, void* stream);
+
+/* out = {threads per workgroup, items per thread, Q, W_MAX, the exponent of lambda (-10)}: a workgroup takes out[0] * out[1] vertices
+ * or faces. */
+int dgs_simplify_layout(int out[5]);
 
 #ifdef __cplusplus
 }
