@@ -4,6 +4,9 @@
 //   knn_refine_kernel: exact answer again from last step's indices; the seed bounds the search, 32-node blocks are culled by
 //     their 3-D bounding boxes.
 //   knn_refine_mfma_kernel: the same with a dense full-distance filter on the matrix cores (split bf16 operands).
+// Contract of all three: every stored index is in [0, M), whatever the inputs hold, and the three agree bit for bit.  A slot that
+// no node fills -- all distances of the point are NaN or infinite (a non-finite coordinate, or a point so far out that the squares
+// overflow) -- holds index 0 (and dist2 = inf in the plain scan).  The result feeds the skinning kernels' gathers unchecked.
 // Each kernel has its launch_* templates behind it; dispatch_K turns the run-time K into the template argument.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -582,8 +585,11 @@ __global__ void __launch_bounds__(kRmThreads) knn_refine_mfma_kernel(int N, int 
     int bi[K];
 #pragma unroll
     for (int k = 0; k < K; k++) { bd[k] = INFINITY; bi[k] = 0x7fffffff; }
+    // an infinite distance (a point with an infinite coordinate, or so far out that the square overflows) is never inserted, like
+    // in the plain scan, where inf < inf is false; a NaN distance fails every comparison.  An unfilled slot keeps 0x7fffffff and
+    // is stored as 0 (below): what the other two kernels' lists start with
     auto offer = [&](float dj, int j) {
-        if (dj < bd[K - 1] || (dj == bd[K - 1] && j < bi[K - 1])) {
+        if (dj < bd[K - 1] || (dj == bd[K - 1] && dj < INFINITY && j < bi[K - 1])) {
             bd[K - 1] = dj; bi[K - 1] = j;
 #pragma unroll
             for (int k = K - 1; k > 0; k--) {
@@ -621,7 +627,7 @@ __global__ void __launch_bounds__(kRmThreads) knn_refine_mfma_kernel(int N, int 
 #pragma unroll
         for (int k = 0; k < K; k++) offer(od[k], oi[k]);
 #pragma unroll
-        for (int k = 0; k < K; k++) idx[(size_t)p * K + k] = bi[k];
+        for (int k = 0; k < K; k++) idx[(size_t)p * K + k] = bi[k] == 0x7fffffff ? 0 : bi[k];
     }
     }   // groups
 }

@@ -569,8 +569,12 @@ def knn_indices2(x1, x2, nodes, K, seed=None, mode="box"):
     """knn_indices(cat([x1, x2], 1), nodes, K) without materialising the concatenation (x2 may be a column slice).
     seed: an int64 [N,K] tensor holding an earlier answer (e.g. last step's); it is refined IN PLACE to the exact
     current answer and returned (dgs_knn_refine: ~3x cheaper than the plain scan, exact for any seed content).  mode: "box" = 3-D
-    culling, "mfma" = dense scores on the matrix cores (dgs_knn_refine_mode; ControlNodes.pick_knn_refine chooses)."""
+    culling, "mfma" = dense scores on the matrix cores (dgs_knn_refine_mode; ControlNodes.pick_knn_refine chooses).
+    With or without a seed the library gets raw pointers and one row stride: x1 and nodes must be contiguous, the columns of x2
+    adjacent, all three float32 (RuntimeError otherwise)."""
     lib = load()
+    if not (x1.is_contiguous() and nodes.is_contiguous() and x2.stride(1) == 1 and x1.dtype == x2.dtype == nodes.dtype == torch.float32):
+        raise RuntimeError("knn_indices2: fp32 row-major inputs expected")
     if seed is not None:
         N = x1.shape[0]
         if not (seed.shape == (N, K) and seed.dtype == torch.int64 and seed.is_contiguous() and x1.shape[1] >= 3
@@ -587,8 +591,6 @@ def knn_indices2(x1, x2, nodes, K, seed=None, mode="box"):
         return seed
     x1, nodes = x1.detach(), nodes.detach()
     x2 = x2.detach()
-    if not (x1.is_contiguous() and nodes.is_contiguous() and x2.stride(1) == 1 and x1.dtype == x2.dtype == nodes.dtype == torch.float32):
-        raise RuntimeError("knn_indices2: fp32 row-major inputs expected")
     N = x1.shape[0]
     idx = torch.empty((N, K), dtype=torch.int64, device=x1.device)
     with torch.cuda.device(x1.device):

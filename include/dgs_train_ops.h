@@ -38,7 +38,10 @@ int dgs_ssim_backward(int C, int H, int W, const float* img1, const float* img2,
                       void* stream);
 
 /* Brute-force K nearest neighbours under squared L2, ascending, ties to the lower index.
- * x: [N,D], nodes: [M,D], 1 <= D <= 16, 1 <= K <= 4, K <= M.  idx: [N,K] int64.  dist2 (may be NULL): [N,K]. */
+ * x: [N,D], nodes: [M,D], 1 <= D <= 16, 1 <= K <= 4, K <= M.  idx: [N,K] int64.  dist2 (may be NULL): [N,K].
+ * Every stored index is in [0, M), whatever the inputs hold: a slot no node fills (every distance of the point NaN or infinite:
+ * a non-finite coordinate, or squares that overflow) holds index 0 and dist2 = inf.  dgs_knn_points2 and dgs_knn_refine[_mode]
+ * keep the same contract and return the same indices bit for bit. */
 int dgs_knn_points(int N, int M, int D, int K, const float* x, const float* nodes, long long* idx, float* dist2,
                    void* stream);
 
