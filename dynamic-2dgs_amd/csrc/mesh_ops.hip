@@ -1,7 +1,7 @@
 // libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion of rendered depth maps, marching tetrahedra, the all-pairs
 // nearest-neighbour and closest-triangle searches and the earth mover's distance (an auction solver) of the mesh metrics, the
-// z-buffer triangle rasterizer of the mesh images, the connected components of the mesh clean-up and the quadric vertex
-// clustering of the mesh simplification, gfx950.
+// z-buffer triangle rasterizer of the mesh images, the connected components of the mesh clean-up, the quadric vertex
+// clustering of the mesh simplification and the Laplacian / Taubin steps of the mesh smoothing, gfx950.
 // Compiled with -ffp-contract=off: every fp32 operation of the kernels rounds on its own, which is what makes the result equal to
 // the PyTorch statement of the same arithmetic (dgs_amd/mesh.py) instead of close to it.
 // The kernels live in one header per family, included in the order they were written; this file is the C ABI: the argument checks
@@ -83,6 +83,13 @@ int search(const Search& s, long long n_query, const float* query, long long n_s
     if (e != hipSuccess) return fail(-2, w + " (init): " + hipGetErrorString(e));
     launch(dim3((unsigned)blocks, (unsigned)slices), chunk);
     return launched(s.what);
+}
+
+// One step of dgs_smooth_steps for a compile-time channel count.
+template <int C>
+void smooth_launch(dim3 grid, hipStream_t st, long long n_vertices, const long long* offsets, const int* neighbours, long long n_entries, int mode,
+                   float s, const unsigned char* pinned, const float* in, float* out) {
+    hipLaunchKernelGGL(smooth_step_kernel<C>, grid, dim3(SMOOTH_THREADS), 0, st, n_vertices, offsets, neighbours, n_entries, mode, s, pinned, in, out);
 }
 }  // namespace
 
@@ -363,6 +370,47 @@ int dgs_simplify_solve(long long n_clusters, const long long* rows, const float*
 
 int dgs_simplify_layout(int out[5]) {
     return layout("dgs_simplify_layout", out, {SIMP_THREADS, SIMP_ITEMS_PER_THREAD, SIMP_Q, SIMP_W_MAX, SIMP_LAMBDA_EXP});
+}
+
+int dgs_smooth_steps(long long n_vertices, const long long* offsets, const int* neighbours, long long n_entries, int C, int mode,
+                     const float* factors, int n_steps, const unsigned char* pinned, float* x, float* tmp, void* stream) {
+    if (n_vertices < 0 || n_entries < 0 || n_steps < 0) return fail(-1, "dgs_smooth_steps: negative count");
+    if (n_vertices >= (1LL << 31) || n_entries >= (1LL << 31)) return fail(-1, "dgs_smooth_steps: every count must be below 2^31 (ids are int32)");
+    if (C < 1 || C > SMOOTH_MAX_C) return fail(-1, "dgs_smooth_steps: C must be in [1, " + std::to_string(SMOOTH_MAX_C) + "]");
+    if (mode != 0 && mode != 1) return fail(-1, "dgs_smooth_steps: mode must be 0 (laplacian) or 1 (simple)");
+    if (n_steps > SMOOTH_MAX_STEPS) return fail(-1, "dgs_smooth_steps: n_steps must be at most " + std::to_string(SMOOTH_MAX_STEPS) + " (dgs_smooth_layout)");
+    if ((n_steps > 0 && !factors) || (n_vertices > 0 && (!offsets || !x || !tmp)) || (n_entries > 0 && !neighbours))
+        return fail(-1, "dgs_smooth_steps: null pointer");
+    for (int k = 0; k < n_steps; ++k)
+        if (!std::isfinite(factors[k])) return fail(-1, "dgs_smooth_steps: factor " + std::to_string(k) + " is not finite");
+    if (n_steps == 0 || n_vertices == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((n_vertices + SMOOTH_VERTS_PER_BLOCK - 1) / SMOOTH_VERTS_PER_BLOCK));     // n_vertices < 2^31: below 2^23 workgroups
+    float *src = x, *dst = tmp;
+    for (int k = 0; k < n_steps; ++k) {
+        const float s = factors[k];
+        switch (C) {
+            case 1: smooth_launch<1>(grid, st, n_vertices, offsets, neighbours, n_entries, mode, s, pinned, src, dst); break;
+            case 2: smooth_launch<2>(grid, st, n_vertices, offsets, neighbours, n_entries, mode, s, pinned, src, dst); break;
+            case 3: smooth_launch<3>(grid, st, n_vertices, offsets, neighbours, n_entries, mode, s, pinned, src, dst); break;
+            case 4: smooth_launch<4>(grid, st, n_vertices, offsets, neighbours, n_entries, mode, s, pinned, src, dst); break;
+            case 5: smooth_launch<5>(grid, st, n_vertices, offsets, neighbours, n_entries, mode, s, pinned, src, dst); break;
+            case 6: smooth_launch<6>(grid, st, n_vertices, offsets, neighbours, n_entries, mode, s, pinned, src, dst); break;
+            case 7: smooth_launch<7>(grid, st, n_vertices, offsets, neighbours, n_entries, mode, s, pinned, src, dst); break;
+            default: smooth_launch<8>(grid, st, n_vertices, offsets, neighbours, n_entries, mode, s, pinned, src, dst); break;
+        }
+        if (int rc = launched("dgs_smooth_steps")) return rc;
+        std::swap(src, dst);
+    }
+    if (src != x) {                                                        // an odd count left the result in tmp
+        hipError_t e = hipMemcpyAsync(x, tmp, (size_t)n_vertices * C * sizeof(float), hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) return fail(-2, std::string("dgs_smooth_steps (copy): ") + hipGetErrorString(e));
+    }
+    return 0;
+}
+
+int dgs_smooth_layout(int out[4]) {
+    return layout("dgs_smooth_layout", out, {SMOOTH_THREADS, SMOOTH_VERTS_PER_BLOCK, SMOOTH_MAX_C, SMOOTH_MAX_STEPS});
 }
 
 }  // extern "C"

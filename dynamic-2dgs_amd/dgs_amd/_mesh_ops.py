@@ -1,7 +1,7 @@
 """ctypes binding of libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion, marching tetrahedra, the all-pairs nearest-neighbour
-and closest-triangle searches, the auction solver of the earth mover's distance, the z-buffer triangle rasterizer, the connected components and the
-quadric vertex clustering for gfx950, used by dgs_amd.mesh, dgs_amd.mesh_metrics, dgs_amd.mesh_render, dgs_amd.mesh_clean and
-dgs_amd.mesh_simplify when the data lives on a HIP device.  CPU tensors use the PyTorch /
+and closest-triangle searches, the auction solver of the earth mover's distance, the z-buffer triangle rasterizer, the connected components, the
+quadric vertex clustering and the smoothing steps for gfx950, used by dgs_amd.mesh, dgs_amd.mesh_metrics, dgs_amd.mesh_render,
+dgs_amd.mesh_clean, dgs_amd.mesh_simplify and dgs_amd.mesh_smooth when the data lives on a HIP device.  CPU tensors use the PyTorch /
 NumPy statements in those modules."""
 import ctypes
 import os
@@ -46,6 +46,9 @@ _SIGNATURES = {
     "dgs_simplify_accumulate": (_ci, [_ll, _vp, _vp, _ll, _vp, _vp, _ll, _vp, _cf, _vp, _vp]),
     "dgs_simplify_solve": (_ci, [_ll, _vp, _vp, _cf, _ci, _vp, _vp, _vp]),
     "dgs_simplify_layout": (_ci, _LAYOUT),
+    # Laplacian / Taubin smoothing (its kernel closes mesh_cc_kernels.h)
+    "dgs_smooth_steps": (_ci, [_ll, _vp, _vp, _ll, _ci, _ci, _vp, _ci, _vp, _vp, _vp, _vp]),
+    "dgs_smooth_layout": (_ci, _LAYOUT),
 }
 _SOURCES = ["mesh_ops.hip", "mesh_common.h", "mesh_fusion_kernels.h", "mesh_search_kernels.h", "mesh_raster_kernels.h", "mesh_cc_kernels.h"]
 _LIB = _dgs_build.NativeLibrary(
@@ -346,3 +349,41 @@ def simplify_solve(rows, centres, cell, quadric=True, with_colors=False):
         rc = lib.dgs_simplify_solve(C, ptr(rows), ptr(centres), float(cell), 1 if quadric else 0, ptr(vertices), ptr(colors), _stream(dev))
     _check(lib, rc, "dgs_simplify_solve")
     return vertices, colors
+
+
+def smooth_layout():
+    """(threads per workgroup, vertices per workgroup, largest C, largest n_steps of one call) of dgs_smooth_steps."""
+    return _layout("dgs_smooth_layout", 4)
+
+
+def smooth_steps(offsets, neighbours, x, mode, factors, pinned=None, tmp=None):
+    """dgs_smooth_steps, in place on x [V,C] (fp32, contiguous, C in [1, 8]) -> x: one step per entry of factors (Python numbers,
+    taken as fp32) of mode 0 (laplacian) or 1 (simple) over the rows offsets [V+1] int64 / neighbours [E] int32
+    (mesh_smooth.vertex_adjacency).  pinned: [V] uint8 or bool, or None; tmp: an optional buffer like x to reuse.  At most
+    smooth_layout()[3] steps a call."""
+    lib = load()
+    dev = x.device
+    _f32(x, "x")
+    if x.dim() != 2:
+        raise RuntimeError("smooth_steps: x [V,C] is expected")
+    V, C = x.shape
+    if not (offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.shape == (V + 1,)):
+        raise RuntimeError("smooth_steps: offsets must be a contiguous int64 HIP tensor [V+1]")
+    if not (neighbours.is_cuda and neighbours.dtype == torch.int32 and neighbours.is_contiguous() and neighbours.dim() == 1):
+        raise RuntimeError("smooth_steps: neighbours must be a contiguous int32 HIP tensor [E]")
+    if pinned is not None:
+        if not (pinned.is_cuda and pinned.dtype in (torch.uint8, torch.bool) and pinned.is_contiguous() and pinned.shape == (V,)):
+            raise RuntimeError("smooth_steps: pinned must be a contiguous uint8 or bool HIP tensor [V]")
+    if tmp is None:
+        tmp = torch.empty_like(x)
+    elif not (tmp.is_cuda and tmp.dtype == torch.float32 and tmp.is_contiguous() and tmp.shape == x.shape) or tmp.data_ptr() == x.data_ptr():
+        raise RuntimeError("smooth_steps: tmp must be another contiguous fp32 HIP tensor of the shape of x")
+    if any(t is not None and t.device != dev for t in (offsets, neighbours, pinned, tmp)):
+        raise RuntimeError("smooth_steps: every tensor must live on the device of x")
+    host = (ctypes.c_float * max(len(factors), 1))(*[float(s) for s in factors])
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    with torch.cuda.device(dev):
+        rc = lib.dgs_smooth_steps(V, ptr(offsets), ptr(neighbours), neighbours.numel(), C, int(mode), ctypes.cast(host, ctypes.c_void_p), len(factors),
+                                  ptr(pinned), ptr(x), ptr(tmp), _stream(dev))
+    _check(lib, rc, "dgs_smooth_steps")
+    return x

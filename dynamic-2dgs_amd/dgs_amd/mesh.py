@@ -331,13 +331,15 @@ def keep_largest_components(vertices, faces, colors=None, n_keep=1000, min_faces
 # ---- the product ----------------------------------------------------------------------------------------------------------------
 def extract_meshes(model_path, data_path, times=None, voxel_size=0.004, depth_trunc=6.0, n_keep=1000, out_dir=None, iteration=-1,
                    device="cuda:0", white_background=False, alpha_min=0.5, bounds=None, quantile=0.01, margin=None, view_chunk=32,
-                   min_faces=50, rasterizer_cls=None, log=None, simplify_cell=None):
+                   min_faces=50, rasterizer_cls=None, log=None, simplify_cell=None, smooth_iterations=None, smooth_method="taubin"):
     """render_mesh.py:169-219: restore() the checkpoint, take the training cameras of the dataset, and for every time (default: the
     times of the test split) render them all at that time, fuse, extract, filter and write <out_dir>/frame_<i>.ply
     (out_dir default: <model_path>/train/ours_<iteration>).  bounds: (lo, hi) of the volume; default: bounds_from_surfels of the
     deformed surfel positions at that time, margin 10 voxels + the truncation.  simplify_cell: if given, the filtered mesh goes
-    through mesh_simplify.simplify_mesh with that cell size before it is written (None: written as extracted).  Returns the list
-    of files written."""
+    through mesh_simplify.simplify_mesh with that cell size before it is written (None: written as extracted).
+    smooth_iterations: if given, the filtered mesh first goes through mesh_smooth.smooth_mesh(method=smooth_method) with that many
+    iterations -- before the simplification, whose plane quadrics then see cleaner normals (None: nothing is called).  Returns the
+    list of files written."""
     from . import io as dio
     from .fit import restore
     device = torch.device(device)
@@ -370,6 +372,9 @@ def extract_meshes(model_path, data_path, times=None, voxel_size=0.004, depth_tr
             v, f, c = filter_components(v, f, c, n_keep=n_keep, min_faces=min_faces)
         else:
             v, f, c = keep_largest_components(v, f, c, n_keep=n_keep, min_faces=min_faces)
+        if smooth_iterations is not None:                # still where it lies: the voxel staircase goes before the quadrics see it
+            from .mesh_smooth import smooth_mesh
+            v, f, c = smooth_mesh(v, f, c, method=smooth_method, iterations=smooth_iterations)
         if simplify_cell is not None:                    # still where it lies: vertex clustering with quadric placement
             from .mesh_simplify import simplify_mesh
             v, f, c = simplify_mesh(v, f, c, cell_size=simplify_cell)
@@ -395,9 +400,12 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--white-background", action="store_true")
     ap.add_argument("--simplify-cell", type=float, default=None, help="simplify every mesh by vertex clustering with this cell size (default: no)")
+    ap.add_argument("--smooth-iterations", type=int, default=None, help="smooth every mesh with this many iterations before it is simplified or written (default: no)")
+    ap.add_argument("--smooth-method", choices=("simple", "laplacian", "taubin"), default="taubin")
     a = ap.parse_args(argv)
     extract_meshes(a.model, a.data, times=a.times, voxel_size=a.voxel_size, depth_trunc=a.depth_trunc, n_keep=a.num_cluster, out_dir=a.out_dir,
-                   iteration=a.iteration, device=a.device, white_background=a.white_background, log=print, simplify_cell=a.simplify_cell)
+                   iteration=a.iteration, device=a.device, white_background=a.white_background, log=print, simplify_cell=a.simplify_cell,
+                   smooth_iterations=a.smooth_iterations, smooth_method=a.smooth_method)
 
 
 if __name__ == "__main__":

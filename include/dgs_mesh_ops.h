@@ -2,7 +2,7 @@
  * dgs_mesh_ops.h -- C ABI of the mesh kernels: depth-map fusion into a truncated signed distance volume, marching tetrahedra over
  * it, the all-pairs nearest-neighbour and closest-triangle searches behind the geometry metrics of dgs_amd/mesh_metrics.py, the
  * z-buffer triangle rasterizer behind the mesh images of dgs_amd/mesh_render.py, the connected components behind
- * dgs_amd/mesh_clean.py, and the quadric vertex clustering behind dgs_amd/mesh_simplify.py.  The first two replace the PyTorch / open3d path of the reference's render_mesh.py:
+ * dgs_amd/mesh_clean.py, the quadric vertex clustering behind dgs_amd/mesh_simplify.py, and the Laplacian / Taubin steps behind dgs_amd/mesh_smooth.py.  The first two replace the PyTorch / open3d path of the reference's render_mesh.py:
  *
  *   dgs_tsdf_integrate          <-  utils/mesh_utils.py:218-266  compute_sdf_perframe + compute_unbounded_tsdf (inv_contraction=None)
  *   dgs_mt_classify / _emit     <-  utils/mesh_utils.py:158-199 / :268-271  volume.extract_triangle_mesh() / marching_cubes_with_contraction
@@ -352,6 +352,45 @@ int dgs_simplify_solve(long long n_clusters, const long long* rows, const float*
 /* out = {threads per workgroup, items per thread, Q, W_MAX, the exponent of lambda (-10)}: a workgroup takes out[0] * out[1] vertices
  * or faces. */
 int dgs_simplify_layout(int out[5]);
+
+/* Mesh smoothing: the Jacobi steps behind dgs_amd/mesh_smooth.py (the roles of open3d's filter_smooth_simple, filter_smooth_laplacian
+ * and filter_smooth_taubin, which the reference's users reach for to take the voxel staircase off an extracted surface).  Version 2
+ * libraries from this commit on also carry the dgs_smooth_* pair; the version number is unchanged because nothing that existed
+ * before changes (the precedent of dgs_tri_*).  UNIFORM (umbrella) WEIGHTS ONLY -- a stated departure from any distance- or
+ * cotangent-weighted variant: every neighbour counts the same, whatever the edge lengths.
+ *
+ * THE ADJACENCY (the wrapper: PyTorch on the tensors' device, dgs_amd/mesh_smooth.py: vertex_adjacency).  A CSR table: offsets
+ * [n_vertices + 1] int64, neighbours [n_entries] int32; row i = neighbours[offsets[i] .. offsets[i + 1]) lists the distinct vertices
+ * j != i that share a face with i, ASCENDING.  Repeated faces do not repeat a neighbour; a face that names a vertex twice is legal.
+ *
+ * ONE STEP, for all C channels of x [n_vertices,C] fp32 and row i of length d, every operation a separately rounded fp32 one
+ * (-ffp-contract=off), the division the IEEE one:
+ *   acc = 0;  for k in row order: acc = acc + x[neighbours[k]]                (sequential per channel)
+ *   mode 0 (laplacian), factor s:  out = x + s * (acc / float(d) - x)
+ *   mode 1 (simple):               out = (x + acc) / float(d + 1)             (the factor is not used)
+ *   out = x where d == 0 or pinned[i] != 0.
+ * Every step reads the complete output of the step before it (Jacobi, never in place).  dgs_amd/mesh_smooth.py: smooth_steps_torch
+ * states the same arithmetic in PyTorch, slot by slot of the rows, and CPU tensors run it: the results are bit-identical.  The order
+ * of a row's sum follows the vertex ids, so THE LAST BITS OF THE RESULT DEPEND ON THE VERTEX NUMBERING: renumbering a mesh changes
+ * them (and nothing else).  laplacian x n: n steps with lam;  taubin x n: n times (a step with lam, a step with mu), 2 n steps;
+ * simple x n: n steps of mode 1.
+ *
+ * dgs_smooth_steps: one call enqueues all n_steps launches on `stream`, step k with factors[k], ping-ponging between x and tmp
+ * [n_vertices,C] (two different buffers: no launch reads what it writes, no kernel waits for another workgroup).  THE RESULT IS
+ * ALWAYS IN x: an odd count ends with one device-to-device copy on the same stream; tmp holds unspecified values afterwards.
+ *   factors [n_steps]: HOST memory, read before the call returns;   pinned [n_vertices] bytes in device memory, or NULL for none
+ *   C in [1, 8]: a thread per vertex keeps its C sums in registers.  A row of thousands of entries (the hub of a fan) is walked by
+ *   one thread: correct, and as slow as that sounds.
+ * A row range is clamped to [0, n_entries] and a neighbour id outside [0, n_vertices) adds nothing: index guards, so no address can
+ * leave a buffer; the Python wrapper produces no such input.
+ * Refused with a negative status before any launch: a negative count, n_vertices or n_entries >= 2^31, C outside [1, 8], a mode
+ * other than 0 or 1, n_steps above dgs_smooth_layout()[3], a null pointer with a non-zero count, a factor that is not finite.
+ * n_steps == 0 or n_vertices == 0 returns 0 and launches nothing. */
+int dgs_smooth_steps(long long n_vertices, const long long* offsets, const int* neighbours, long long n_entries, int C, int mode,
+                     const float* factors, int n_steps, const unsigned char* pinned, float* x, float* tmp, void* stream);
+
+/* out = {threads per workgroup, vertices per workgroup, largest C, largest n_steps of one call}. */
+int dgs_smooth_layout(int out[4]);
 
 #ifdef __cplusplus
 }
