@@ -1,7 +1,8 @@
 // libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion of rendered depth maps, marching tetrahedra, the all-pairs
 // nearest-neighbour and closest-triangle searches and the earth mover's distance (an auction solver) of the mesh metrics, the
 // z-buffer triangle rasterizer of the mesh images, the connected components of the mesh clean-up, the quadric vertex
-// clustering of the mesh simplification and the Laplacian / Taubin steps of the mesh smoothing, gfx950.
+// clustering of the mesh simplification, the Laplacian / Taubin steps of the mesh smoothing and the quadric edge collapse of the
+// mesh decimation, gfx950.
 // Compiled with -ffp-contract=off: every fp32 operation of the kernels rounds on its own, which is what makes the result equal to
 // the PyTorch statement of the same arithmetic (dgs_amd/mesh.py) instead of close to it.
 // The kernels live in one header per family, included in the order they were written; this file is the C ABI: the argument checks
@@ -10,6 +11,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <initializer_list>
 #include <string>
 
 #include "../../include/dgs_mesh_ops.h"
@@ -91,6 +93,25 @@ void smooth_launch(dim3 grid, hipStream_t st, long long n_vertices, const long l
                    float s, const unsigned char* pinned, const float* in, float* out) {
     hipLaunchKernelGGL(smooth_step_kernel<C>, grid, dim3(SMOOTH_THREADS), 0, st, n_vertices, offsets, neighbours, n_entries, mode, s, pinned, in, out);
 }
+
+// The dgs_decimate_* calls: every count in [0, 2^31) (ids are int32, and the quadric sums are sized for it) ...
+int dec_counts(const char* what, std::initializer_list<long long> counts) {
+    for (long long n : counts) {
+        if (n < 0) return fail(-1, std::string(what) + ": negative count");
+        if (n >= (1LL << 31)) return fail(-1, std::string(what) + ": every count must be below 2^31 (ids are int32)");
+    }
+    return 0;
+}
+
+// ... and q_bits in [1, Q_MAX] with n_faces * 2^q_bits <= 2^Q_BUDGET: the overflow bound of include/dgs_mesh_ops.h.
+int dec_bits(const char* what, int q_bits, long long n_faces) {
+    if (q_bits < 1 || q_bits > DEC_Q_MAX || (n_faces > 0 && n_faces > (1LL << (DEC_Q_BUDGET - q_bits))))
+        return fail(-1, std::string(what) + ": q_bits must be in [1, " + std::to_string(DEC_Q_MAX) + "] with n_faces * 2^q_bits <= 2^" +
+                            std::to_string(DEC_Q_BUDGET) + " (the quadric sums could overflow)");
+    return 0;
+}
+
+dim3 dec_blocks(long long n) { return dim3((unsigned)((n + DEC_THREADS - 1) / DEC_THREADS)); }      // n < 2^31: below 2^23 workgroups
 }  // namespace
 
 extern "C" {
@@ -411,6 +432,92 @@ int dgs_smooth_steps(long long n_vertices, const long long* offsets, const int* 
 
 int dgs_smooth_layout(int out[4]) {
     return layout("dgs_smooth_layout", out, {SMOOTH_THREADS, SMOOTH_VERTS_PER_BLOCK, SMOOTH_MAX_C, SMOOTH_MAX_STEPS});
+}
+
+int dgs_decimate_quadrics(long long n_vertices, const float* pos, long long n_faces, const int* faces, float mean_len, int q_bits,
+                          long long* rows, void* stream) {
+    if (int rc = dec_counts("dgs_decimate_quadrics", {n_vertices, n_faces})) return rc;
+    if (int rc = dec_bits("dgs_decimate_quadrics", q_bits, n_faces)) return rc;
+    if (!(mean_len > 0.0f) || !std::isfinite(mean_len)) return fail(-1, "dgs_decimate_quadrics: mean_len must be positive and finite");
+    if ((n_vertices > 0 && (!pos || !rows)) || (n_faces > 0 && !faces)) return fail(-1, "dgs_decimate_quadrics: null pointer");
+    if (n_vertices == 0) return 0;
+    hipError_t e = hipMemsetAsync(rows, 0, (size_t)n_vertices * DEC_ROW * sizeof(long long), (hipStream_t)stream);
+    if (e != hipSuccess) return fail(-2, std::string("dgs_decimate_quadrics (clear): ") + hipGetErrorString(e));
+    if (n_faces == 0) return 0;
+    hipLaunchKernelGGL(dec_quadric_kernel, dec_blocks(n_faces), dim3(DEC_THREADS), 0, (hipStream_t)stream, n_faces, faces, n_vertices, pos, mean_len,
+                       std::ldexp(1.0, q_bits), rows);
+    return launched("dgs_decimate_quadrics");
+}
+
+int dgs_decimate_edges(long long n_vertices, const float* pos, const long long* rows, const unsigned char* flags, long long n_faces,
+                       const int* faces, long long n_edges, const int* edges, const long long* adj_offsets, const int* adj, long long n_adj,
+                       const long long* vf_offsets, const int* vf, long long n_vf, int q_bits, float max_cost, float* cost, float* place,
+                       unsigned char* valid, void* stream) {
+    if (int rc = dec_counts("dgs_decimate_edges", {n_vertices, n_faces, n_edges, n_adj, n_vf})) return rc;
+    if (int rc = dec_bits("dgs_decimate_edges", q_bits, n_faces)) return rc;
+    if (!(max_cost >= 0.0f)) return fail(-1, "dgs_decimate_edges: max_cost must be >= 0 (+inf for no bound)");
+    if ((n_vertices > 0 && (!pos || !rows || !flags || !adj_offsets || !vf_offsets)) || (n_faces > 0 && !faces) || (n_adj > 0 && !adj) ||
+        (n_vf > 0 && !vf) || (n_edges > 0 && (!edges || !cost || !place || !valid)))
+        return fail(-1, "dgs_decimate_edges: null pointer");
+    if (n_edges == 0) return 0;
+    hipLaunchKernelGGL(dec_edge_kernel, dec_blocks(n_edges), dim3(DEC_THREADS), 0, (hipStream_t)stream, n_vertices, pos, rows, flags, n_faces, faces,
+                       n_edges, edges, adj_offsets, adj, n_adj, vf_offsets, vf, n_vf, std::ldexp(1.0, -q_bits), max_cost, cost, place, valid);
+    return launched("dgs_decimate_edges");
+}
+
+int dgs_decimate_select(long long n_vertices, long long n_edges, const int* edges, const float* cost, const unsigned char* compete,
+                        unsigned long long* m1, unsigned long long* m2, unsigned char* selected, void* stream) {
+    if (int rc = dec_counts("dgs_decimate_select", {n_vertices, n_edges})) return rc;
+    if ((n_vertices > 0 && (!m1 || !m2)) || (n_edges > 0 && (!edges || !cost || !compete || !selected))) return fail(-1, "dgs_decimate_select: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (n_vertices > 0) {
+        hipLaunchKernelGGL(dec_fill_kernel, dec_blocks(n_vertices), dim3(DEC_THREADS), 0, st, n_vertices, m1, DEC_NO_KEY);
+        if (int rc = launched("dgs_decimate_select (init)")) return rc;
+    }
+    if (n_edges > 0 && n_vertices > 0) {
+        hipLaunchKernelGGL(dec_select_kernel<1>, dec_blocks(n_edges), dim3(DEC_THREADS), 0, st, n_vertices, n_edges, edges, cost, compete, m1, m2, selected);
+        if (int rc = launched("dgs_decimate_select (pass 1)")) return rc;
+    }
+    if (n_vertices > 0) {
+        hipError_t e = hipMemcpyAsync(m2, m1, (size_t)n_vertices * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) return fail(-2, std::string("dgs_decimate_select (copy): ") + hipGetErrorString(e));
+    }
+    if (n_edges == 0) return 0;
+    if (n_vertices > 0) {
+        hipLaunchKernelGGL(dec_select_kernel<2>, dec_blocks(n_edges), dim3(DEC_THREADS), 0, st, n_vertices, n_edges, edges, cost, compete, m1, m2, selected);
+        if (int rc = launched("dgs_decimate_select (pass 2)")) return rc;
+    }
+    hipLaunchKernelGGL(dec_select_kernel<3>, dec_blocks(n_edges), dim3(DEC_THREADS), 0, st, n_vertices, n_edges, edges, cost, compete, m1, m2, selected);
+    return launched("dgs_decimate_select (pass 3)");
+}
+
+int dgs_decimate_apply(long long n_vertices, float* pos, long long* rows, float* colors, const unsigned char* flags, unsigned char* moved, int* vmap,
+                       long long n_edges, const int* edges, const float* place, long long n_sel, const int* sel, long long n_faces, int* faces,
+                       unsigned char* keep, void* stream) {
+    if (int rc = dec_counts("dgs_decimate_apply", {n_vertices, n_edges, n_sel, n_faces})) return rc;
+    if ((n_vertices > 0 && (!pos || !rows || !flags || !moved || !vmap)) || (n_edges > 0 && (!edges || !place)) || (n_sel > 0 && !sel) ||
+        (n_faces > 0 && (!faces || !keep)))
+        return fail(-1, "dgs_decimate_apply: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (n_vertices > 0) {
+        hipLaunchKernelGGL(dec_iota_kernel, dec_blocks(n_vertices), dim3(DEC_THREADS), 0, st, n_vertices, vmap);
+        if (int rc = launched("dgs_decimate_apply (init)")) return rc;
+    }
+    if (n_sel > 0 && n_edges > 0 && n_vertices > 0) {
+        hipLaunchKernelGGL(dec_collapse_kernel, dec_blocks(n_sel), dim3(DEC_THREADS), 0, st, n_vertices, pos, rows, colors, flags, moved, vmap, n_edges,
+                           edges, place, n_sel, sel);
+        if (int rc = launched("dgs_decimate_apply (collapse)")) return rc;
+    }
+    if (n_faces > 0) {
+        hipLaunchKernelGGL(dec_reindex_kernel, dec_blocks(n_faces), dim3(DEC_THREADS), 0, st, n_faces, faces, n_vertices, vmap, keep);
+        if (int rc = launched("dgs_decimate_apply (faces)")) return rc;
+    }
+    return 0;
+}
+
+int dgs_decimate_layout(int out[8]) {
+    return layout("dgs_decimate_layout", out, {DEC_THREADS, DEC_ITEMS_PER_THREAD, DEC_Q_MAX, DEC_Q_BUDGET, DEC_W_MAX, DEC_LAMBDA_EXP, DEC_MIN_VALENCE,
+                                               DEC_LEN_BITS});
 }
 
 }  // extern "C"

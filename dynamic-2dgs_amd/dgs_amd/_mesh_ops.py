@@ -1,7 +1,8 @@
 """ctypes binding of libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion, marching tetrahedra, the all-pairs nearest-neighbour
 and closest-triangle searches, the auction solver of the earth mover's distance, the z-buffer triangle rasterizer, the connected components, the
-quadric vertex clustering and the smoothing steps for gfx950, used by dgs_amd.mesh, dgs_amd.mesh_metrics, dgs_amd.mesh_render,
-dgs_amd.mesh_clean, dgs_amd.mesh_simplify and dgs_amd.mesh_smooth when the data lives on a HIP device.  CPU tensors use the PyTorch /
+quadric vertex clustering, the smoothing steps and the edge collapse rounds for gfx950, used by dgs_amd.mesh, dgs_amd.mesh_metrics,
+dgs_amd.mesh_render, dgs_amd.mesh_clean, dgs_amd.mesh_simplify, dgs_amd.mesh_smooth and dgs_amd.mesh_decimate when the data lives on a
+HIP device.  CPU tensors use the PyTorch /
 NumPy statements in those modules."""
 import ctypes
 import os
@@ -49,6 +50,12 @@ _SIGNATURES = {
     # Laplacian / Taubin smoothing (its kernel closes mesh_cc_kernels.h)
     "dgs_smooth_steps": (_ci, [_ll, _vp, _vp, _ll, _ci, _ci, _vp, _ci, _vp, _vp, _vp, _vp]),
     "dgs_smooth_layout": (_ci, _LAYOUT),
+    # quadric edge collapse in rounds (its kernels close mesh_cc_kernels.h)
+    "dgs_decimate_quadrics": (_ci, [_ll, _vp, _ll, _vp, _cf, _ci, _vp, _vp]),
+    "dgs_decimate_edges": (_ci, [_ll, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _vp, _ll, _vp, _vp, _ll, _ci, _cf, _vp, _vp, _vp, _vp]),
+    "dgs_decimate_select": (_ci, [_ll, _ll] + [_vp] * 7),
+    "dgs_decimate_apply": (_ci, [_ll] + [_vp] * 6 + [_ll, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _vp]),
+    "dgs_decimate_layout": (_ci, _LAYOUT),
 }
 _SOURCES = ["mesh_ops.hip", "mesh_common.h", "mesh_fusion_kernels.h", "mesh_search_kernels.h", "mesh_raster_kernels.h", "mesh_cc_kernels.h"]
 _LIB = _dgs_build.NativeLibrary(
@@ -387,3 +394,98 @@ def smooth_steps(offsets, neighbours, x, mode, factors, pinned=None, tmp=None):
                                   ptr(pinned), ptr(x), ptr(tmp), _stream(dev))
     _check(lib, rc, "dgs_smooth_steps")
     return x
+
+
+def decimate_layout():
+    """(threads per workgroup, items per thread, Q_MAX, Q_BUDGET, W_MAX, exponent of lambda, least valence of an interior opposite
+    vertex, fixed-point bits of mean_len) of the dgs_decimate_* calls."""
+    return _layout("dgs_decimate_layout", 8)
+
+
+def _dec(t, dtype, shape, what):
+    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise RuntimeError("%s must be a contiguous %s HIP tensor %s" % (what, str(dtype).replace("torch.", ""), list(shape)))
+    return t
+
+
+_ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+
+
+def decimate_quadrics(pos, faces, mean_len, q_bits):
+    """dgs_decimate_quadrics -> rows [V,10] int64 on the device of pos [V,3] (the frame) for faces [F,3] int32."""
+    lib = load()
+    dev = pos.device
+    V, F = pos.shape[0], faces.shape[0]
+    _dec(pos, torch.float32, (V, 3), "decimate_quadrics: pos"), _dec(faces, torch.int32, (F, 3), "decimate_quadrics: faces")
+    if faces.device != dev:
+        raise RuntimeError("decimate_quadrics: every tensor must live on the device of pos")
+    rows = torch.empty((V, 10), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.dgs_decimate_quadrics(V, _ptr(pos), F, _ptr(faces), float(mean_len), int(q_bits), _ptr(rows), _stream(dev))
+    _check(lib, rc, "dgs_decimate_quadrics")
+    return rows
+
+
+def decimate_edges(pos, rows, faces, tab, q_bits, max_cost):
+    """dgs_decimate_edges -> (cost [E] fp32, place [E,3] fp32, valid [E] bool) for the tables of mesh_decimate.round_tables."""
+    lib = load()
+    dev = pos.device
+    V, F, E = pos.shape[0], faces.shape[0], tab["edges"].shape[1]
+    _dec(pos, torch.float32, (V, 3), "decimate_edges: pos"), _dec(rows, torch.int64, (V, 10), "decimate_edges: rows")
+    _dec(faces, torch.int32, (F, 3), "decimate_edges: faces"), _dec(tab["edges"], torch.int32, (5, E), "decimate_edges: edges")
+    _dec(tab["flags"], torch.uint8, (V,), "decimate_edges: flags")
+    _dec(tab["adj_offsets"], torch.int64, (V + 1,), "decimate_edges: adj_offsets"), _dec(tab["vf_offsets"], torch.int64, (V + 1,), "decimate_edges: vf_offsets")
+    adj, vf = tab["adj"], tab["vf"]
+    _dec(adj, torch.int32, (adj.numel(),), "decimate_edges: adj"), _dec(vf, torch.int32, (vf.numel(),), "decimate_edges: vf")
+    if any(t.device != dev for t in (rows, faces, tab["edges"], tab["flags"], tab["adj_offsets"], adj, tab["vf_offsets"], vf)):
+        raise RuntimeError("decimate_edges: every tensor must live on the device of pos")
+    cost = torch.empty(E, dtype=torch.float32, device=dev)
+    place = torch.empty((E, 3), dtype=torch.float32, device=dev)
+    valid = torch.empty(E, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.dgs_decimate_edges(V, _ptr(pos), _ptr(rows), _ptr(tab["flags"]), F, _ptr(faces), E, _ptr(tab["edges"]), _ptr(tab["adj_offsets"]),
+                                    _ptr(adj), adj.numel(), _ptr(tab["vf_offsets"]), _ptr(vf), vf.numel(), int(q_bits), float(max_cost), _ptr(cost),
+                                    _ptr(place), _ptr(valid), _stream(dev))
+    _check(lib, rc, "dgs_decimate_edges")
+    return cost, place, valid.bool()
+
+
+def decimate_select(n_vertices, edges, cost, compete):
+    """dgs_decimate_select -> (m1 [V] int64, m2 [V] int64, selected [E] bool) for edges [5,E] int32, cost [E] fp32, compete [E] bool."""
+    lib = load()
+    dev = cost.device
+    V, E = int(n_vertices), edges.shape[1]
+    _dec(edges, torch.int32, (5, E), "decimate_select: edges"), _dec(cost, torch.float32, (E,), "decimate_select: cost")
+    _dec(compete, torch.bool, (E,), "decimate_select: compete")
+    if edges.device != dev or compete.device != dev:
+        raise RuntimeError("decimate_select: every tensor must live on the device of cost")
+    m1 = torch.empty(V, dtype=torch.int64, device=dev)
+    m2 = torch.empty(V, dtype=torch.int64, device=dev)
+    selected = torch.empty(E, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.dgs_decimate_select(V, E, _ptr(edges), _ptr(cost), _ptr(compete), _ptr(m1), _ptr(m2), _ptr(selected), _stream(dev))
+    _check(lib, rc, "dgs_decimate_select")
+    return m1, m2, selected.bool()
+
+
+def decimate_apply(pos, rows, colors, moved, faces, tab, place, sel):
+    """dgs_decimate_apply, in place on pos [V,3], rows [V,10], colors [V,3] or None, moved [V] bool and faces [F,3] int32 (re-indexed)
+    -> (vmap [V] int32, faces, keep [F] bool) for the selected edge ids sel [S] int32."""
+    lib = load()
+    dev = pos.device
+    V, F, E, S = pos.shape[0], faces.shape[0], tab["edges"].shape[1], sel.shape[0]
+    _dec(pos, torch.float32, (V, 3), "decimate_apply: pos"), _dec(rows, torch.int64, (V, 10), "decimate_apply: rows")
+    _dec(moved, torch.bool, (V,), "decimate_apply: moved"), _dec(faces, torch.int32, (F, 3), "decimate_apply: faces")
+    _dec(tab["edges"], torch.int32, (5, E), "decimate_apply: edges"), _dec(tab["flags"], torch.uint8, (V,), "decimate_apply: flags")
+    _dec(place, torch.float32, (E, 3), "decimate_apply: place"), _dec(sel, torch.int32, (S,), "decimate_apply: sel")
+    if colors is not None:
+        _dec(colors, torch.float32, (V, 3), "decimate_apply: colors")
+    if any(t is not None and t.device != dev for t in (rows, colors, moved, faces, tab["edges"], tab["flags"], place, sel)):
+        raise RuntimeError("decimate_apply: every tensor must live on the device of pos")
+    vmap = torch.empty(V, dtype=torch.int32, device=dev)
+    keep = torch.empty(F, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.dgs_decimate_apply(V, _ptr(pos), _ptr(rows), _ptr(colors), _ptr(tab["flags"]), _ptr(moved), _ptr(vmap), E, _ptr(tab["edges"]),
+                                    _ptr(place), S, _ptr(sel), F, _ptr(faces), _ptr(keep), _stream(dev))
+    _check(lib, rc, "dgs_decimate_apply")
+    return vmap, faces, keep.bool()

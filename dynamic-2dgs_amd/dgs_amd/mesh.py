@@ -331,7 +331,8 @@ def keep_largest_components(vertices, faces, colors=None, n_keep=1000, min_faces
 # ---- the product ----------------------------------------------------------------------------------------------------------------
 def extract_meshes(model_path, data_path, times=None, voxel_size=0.004, depth_trunc=6.0, n_keep=1000, out_dir=None, iteration=-1,
                    device="cuda:0", white_background=False, alpha_min=0.5, bounds=None, quantile=0.01, margin=None, view_chunk=32,
-                   min_faces=50, rasterizer_cls=None, log=None, simplify_cell=None, smooth_iterations=None, smooth_method="taubin"):
+                   min_faces=50, rasterizer_cls=None, log=None, simplify_cell=None, smooth_iterations=None, smooth_method="taubin",
+                   decimate_faces=None, decimate_ratio=None):
     """render_mesh.py:169-219: restore() the checkpoint, take the training cameras of the dataset, and for every time (default: the
     times of the test split) render them all at that time, fuse, extract, filter and write <out_dir>/frame_<i>.ply
     (out_dir default: <model_path>/train/ours_<iteration>).  bounds: (lo, hi) of the volume; default: bounds_from_surfels of the
@@ -378,6 +379,9 @@ def extract_meshes(model_path, data_path, times=None, voxel_size=0.004, depth_tr
         if simplify_cell is not None:                    # still where it lies: vertex clustering with quadric placement
             from .mesh_simplify import simplify_mesh
             v, f, c = simplify_mesh(v, f, c, cell_size=simplify_cell)
+        if decimate_faces is not None or decimate_ratio is not None:   # last: edge collapse to a face budget, still a manifold
+            from .mesh_decimate import decimate_mesh
+            v, f, c = decimate_mesh(v, f, c, target_faces=decimate_faces, ratio=decimate_ratio)
         path =os.path.join(out_dir, "frame_{}.ply".format(i))
         dio.write_mesh_ply(path, v, f, c)
         written.append(path)
@@ -402,10 +406,13 @@ def main(argv=None):
     ap.add_argument("--simplify-cell", type=float, default=None, help="simplify every mesh by vertex clustering with this cell size (default: no)")
     ap.add_argument("--smooth-iterations", type=int, default=None, help="smooth every mesh with this many iterations before it is simplified or written (default: no)")
     ap.add_argument("--smooth-method", choices=("simple", "laplacian", "taubin"), default="taubin")
+    ap.add_argument("--decimate-faces", type=int, default=None, help="decimate every mesh by edge collapse to this many faces, last (default: no)")
+    ap.add_argument("--decimate-ratio", type=float, default=None, help="decimate every mesh by edge collapse to this share of its faces, last (default: no)")
     a = ap.parse_args(argv)
     extract_meshes(a.model, a.data, times=a.times, voxel_size=a.voxel_size, depth_trunc=a.depth_trunc, n_keep=a.num_cluster, out_dir=a.out_dir,
                    iteration=a.iteration, device=a.device, white_background=a.white_background, log=print, simplify_cell=a.simplify_cell,
-                   smooth_iterations=a.smooth_iterations, smooth_method=a.smooth_method)
+                   smooth_iterations=a.smooth_iterations, smooth_method=a.smooth_method, decimate_faces=a.decimate_faces,
+                   decimate_ratio=a.decimate_ratio)
 
 
 if __name__ == "__main__":
