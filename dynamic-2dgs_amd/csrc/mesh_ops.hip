@@ -1,8 +1,8 @@
 // libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion of rendered depth maps, marching tetrahedra, the all-pairs
 // nearest-neighbour and closest-triangle searches and the earth mover's distance (an auction solver) of the mesh metrics, the
 // z-buffer triangle rasterizer of the mesh images, the connected components of the mesh clean-up, the quadric vertex
-// clustering of the mesh simplification, the Laplacian / Taubin steps of the mesh smoothing and the quadric edge collapse of the
-// mesh decimation, gfx950.
+// clustering of the mesh simplification, the Laplacian / Taubin steps of the mesh smoothing, the quadric edge collapse of the
+// mesh decimation and the list ranking and ring emission of the mesh hole filling, gfx950.
 // Compiled with -ffp-contract=off: every fp32 operation of the kernels rounds on its own, which is what makes the result equal to
 // the PyTorch statement of the same arithmetic (dgs_amd/mesh.py) instead of close to it.
 // The kernels live in one header per family, included in the order they were written; this file is the C ABI: the argument checks
@@ -112,6 +112,14 @@ int dec_bits(const char* what, int q_bits, long long n_faces) {
 }
 
 dim3 dec_blocks(long long n) { return dim3((unsigned)((n + DEC_THREADS - 1) / DEC_THREADS)); }      // n < 2^31: below 2^23 workgroups
+
+// The frame of dgs_fill_rim and dgs_fill_emit: positions enter the sums as (v - centre) * scale, scale a power of two.
+int fill_frame(const char* what, double cx, double cy, double cz, double scale, FillFrame& fr) {
+    if (!std::isfinite(cx) || !std::isfinite(cy) || !std::isfinite(cz) || !(scale > 0.0) || !std::isfinite(scale) || !std::isfinite(1.0 / scale))
+        return fail(-1, std::string(what) + ": the frame's centre must be finite and its scale positive and finite");
+    fr = FillFrame{{cx, cy, cz}, scale, 1.0 / scale};
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -518,6 +526,78 @@ int dgs_decimate_apply(long long n_vertices, float* pos, long long* rows, float*
 int dgs_decimate_layout(int out[8]) {
     return layout("dgs_decimate_layout", out, {DEC_THREADS, DEC_ITEMS_PER_THREAD, DEC_Q_MAX, DEC_Q_BUDGET, DEC_W_MAX, DEC_LAMBDA_EXP, DEC_MIN_VALENCE,
                                                DEC_LEN_BITS});
+}
+
+int dgs_fill_rank(long long n_nodes, const int* succ, const int* leader, int n_rounds, unsigned long long* buf_a, unsigned long long* buf_b,
+                  int* rank, void* stream) {
+    if (int rc = dec_counts("dgs_fill_rank", {n_nodes})) return rc;
+    if (n_rounds < 0 || n_rounds > FILL_MAX_ROUNDS)
+        return fail(-1, "dgs_fill_rank: n_rounds must be in [0, " + std::to_string(FILL_MAX_ROUNDS) + "] (2^n_rounds nodes are the longest list)");
+    if (n_nodes > 0 && (!succ || !leader || !buf_a || !buf_b || !rank)) return fail(-1, "dgs_fill_rank: null pointer");
+    if (n_nodes > 0 && buf_a == buf_b) return fail(-1, "dgs_fill_rank: buf_a and buf_b must be two buffers (a round reads one and writes the other)");
+    if (n_nodes == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid = dec_blocks(n_nodes);
+    hipLaunchKernelGGL(fill_rank_init_kernel, grid, dim3(FILL_THREADS), 0, st, n_nodes, succ, leader, buf_a);
+    if (int rc = launched("dgs_fill_rank (init)")) return rc;
+    unsigned long long *in = buf_a, *out = buf_b;
+    for (int r = 0; r < n_rounds; ++r) {
+        hipLaunchKernelGGL(fill_rank_round_kernel, grid, dim3(FILL_THREADS), 0, st, n_nodes, in, out);
+        if (int rc = launched("dgs_fill_rank (round)")) return rc;
+        std::swap(in, out);
+    }
+    hipLaunchKernelGGL(fill_rank_final_kernel, grid, dim3(FILL_THREADS), 0, st, n_nodes, leader, in, rank);
+    return launched("dgs_fill_rank (ranks)");
+}
+
+int dgs_fill_rim(long long n_vertices, const float* vertices, const float* colors, long long n_rim, const int* loop_vertices, const int* rim_loop,
+                 long long n_loops, const long long* loop_offsets, double centre_x, double centre_y, double centre_z, double scale, double* S,
+                 double* SC, long long* rows, void* stream) {
+    if (int rc = dec_counts("dgs_fill_rim", {n_vertices, n_rim, n_loops})) return rc;
+    FillFrame fr;
+    if (int rc = fill_frame("dgs_fill_rim", centre_x, centre_y, centre_z, scale, fr)) return rc;
+    if ((n_vertices > 0 && !vertices) || (n_rim > 0 && (!loop_vertices || !rim_loop || !S)) || (n_loops > 0 && (!loop_offsets || !rows)) ||
+        (n_rim > 0 && (colors != nullptr) != (SC != nullptr)))
+        return fail(-1, "dgs_fill_rim: null pointer (colors and SC come together)");
+    if (n_loops == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(rows, 0, (size_t)n_loops * SIMP_ROW * sizeof(long long), st);
+    if (e != hipSuccess) return fail(-2, std::string("dgs_fill_rim (clear): ") + hipGetErrorString(e));
+    if (n_rim == 0) return 0;
+    hipLaunchKernelGGL(fill_rim_kernel, dec_blocks(n_rim), dim3(FILL_THREADS), 0, st, n_vertices, vertices, colors, n_rim, loop_vertices, rim_loop,
+                       n_loops, loop_offsets, fr, S, SC, rows);
+    return launched("dgs_fill_rim");
+}
+
+int dgs_fill_emit(long long n_old, long long n_new, const int* vert_ring, long long n_new_faces, const int* face_ring, long long n_rings,
+                  const int* rings, long long n_loops, const long long* loop_offsets, long long n_rim, const int* loop_vertices,
+                  const long long* rows, const double* S, const double* SC, double centre_x, double centre_y, double centre_z, double scale,
+                  float* vertices_out, float* colors_out, int* faces_out, void* stream) {
+    if (int rc = dec_counts("dgs_fill_emit", {n_old, n_new, n_old + n_new, n_new_faces, n_rings, n_loops, n_rim})) return rc;
+    FillFrame fr;
+    if (int rc = fill_frame("dgs_fill_emit", centre_x, centre_y, centre_z, scale, fr)) return rc;
+    const bool any = n_new > 0 || n_new_faces > 0;
+    if ((n_new > 0 && !vert_ring) || (n_new_faces > 0 && (!face_ring || !faces_out)) || (n_old + n_new > 0 && any && !vertices_out) ||
+        (any && (!rings || !loop_offsets || !loop_vertices || !rows || !S)) || (n_new > 0 && (colors_out != nullptr) != (SC != nullptr)))
+        return fail(-1, "dgs_fill_emit: null pointer (colors_out and SC come together)");
+    if (any && (n_rings == 0 || n_loops == 0 || n_rim == 0)) return fail(-1, "dgs_fill_emit: new vertices or faces without rings, loops or a rim");
+    hipStream_t st = (hipStream_t)stream;
+    if (n_new > 0) {
+        hipLaunchKernelGGL(fill_vertex_kernel, dec_blocks(n_new), dim3(FILL_THREADS), 0, st, n_old, n_new, vert_ring, n_rings, rings, n_loops,
+                           loop_offsets, n_rim, rows, S, SC, fr, vertices_out, colors_out);
+        if (int rc = launched("dgs_fill_emit (vertices)")) return rc;
+    }
+    if (n_new_faces > 0) {
+        hipLaunchKernelGGL(fill_face_kernel, dec_blocks(n_new_faces), dim3(FILL_THREADS), 0, st, n_old + n_new, n_new_faces, face_ring, n_rings, rings,
+                           n_loops, loop_offsets, n_rim, loop_vertices, rows, vertices_out, faces_out);
+        if (int rc = launched("dgs_fill_emit (faces)")) return rc;
+    }
+    return 0;
+}
+
+int dgs_fill_layout(int out[8]) {
+    return layout("dgs_fill_layout", out, {FILL_THREADS, FILL_ITEMS_PER_THREAD, FILL_POS_BITS, FILL_NRM_BITS, FILL_COL_BITS, FILL_RING_COLS,
+                                           FILL_TAPS, FILL_MAX_ROUNDS});
 }
 
 }  // extern "C"

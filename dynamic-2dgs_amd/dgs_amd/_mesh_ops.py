@@ -1,8 +1,8 @@
 """ctypes binding of libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion, marching tetrahedra, the all-pairs nearest-neighbour
 and closest-triangle searches, the auction solver of the earth mover's distance, the z-buffer triangle rasterizer, the connected components, the
-quadric vertex clustering, the smoothing steps and the edge collapse rounds for gfx950, used by dgs_amd.mesh, dgs_amd.mesh_metrics,
-dgs_amd.mesh_render, dgs_amd.mesh_clean, dgs_amd.mesh_simplify, dgs_amd.mesh_smooth and dgs_amd.mesh_decimate when the data lives on a
-HIP device.  CPU tensors use the PyTorch /
+quadric vertex clustering, the smoothing steps, the edge collapse rounds and the hole filling for gfx950, used by dgs_amd.mesh,
+dgs_amd.mesh_metrics, dgs_amd.mesh_render, dgs_amd.mesh_clean, dgs_amd.mesh_simplify, dgs_amd.mesh_smooth, dgs_amd.mesh_decimate and
+dgs_amd.mesh_fill when the data lives on a HIP device.  CPU tensors use the PyTorch /
 NumPy statements in those modules."""
 import ctypes
 import os
@@ -18,7 +18,7 @@ _CSRC = _ops._CSRC
 HIPCC_FLAGS = list(_ops.HIPCC_FLAGS) + ["-ffp-contract=off"]
 # name -> (restype, argtypes) of every function include/dgs_mesh_ops.h declares, grouped like csrc/mesh_ops.hip.  Written by hand:
 # tests/test_cabi_exports.py compares names, arities and return types with the header.
-_ci, _vp, _cf, _ll = ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_longlong
+_ci, _vp, _cf, _ll, _cd = ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_longlong, ctypes.c_double
 _SEARCH = [_ll, _vp, _ll, _vp, _ll, _vp, _vp]         # n_query, query, n_set, set, chunk, best, stream
 _LAYOUT = [ctypes.POINTER(_ci)]
 _SIGNATURES = {
@@ -56,6 +56,11 @@ _SIGNATURES = {
     "dgs_decimate_select": (_ci, [_ll, _ll] + [_vp] * 7),
     "dgs_decimate_apply": (_ci, [_ll] + [_vp] * 6 + [_ll, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _vp]),
     "dgs_decimate_layout": (_ci, _LAYOUT),
+    # hole filling: list ranking, loop sums and smoothed rims, ring emission (its kernels close mesh_cc_kernels.h)
+    "dgs_fill_rank": (_ci, [_ll, _vp, _vp, _ci, _vp, _vp, _vp, _vp]),
+    "dgs_fill_rim": (_ci, [_ll, _vp, _vp, _ll, _vp, _vp, _ll, _vp, _cd, _cd, _cd, _cd, _vp, _vp, _vp, _vp]),
+    "dgs_fill_emit": (_ci, [_ll, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _vp, _vp, _vp, _cd, _cd, _cd, _cd, _vp, _vp, _vp, _vp]),
+    "dgs_fill_layout": (_ci, _LAYOUT),
 }
 _SOURCES = ["mesh_ops.hip", "mesh_common.h", "mesh_fusion_kernels.h", "mesh_search_kernels.h", "mesh_raster_kernels.h", "mesh_cc_kernels.h"]
 _LIB = _dgs_build.NativeLibrary(
@@ -489,3 +494,77 @@ def decimate_apply(pos, rows, colors, moved, faces, tab, place, sel):
                                     _ptr(place), S, _ptr(sel), F, _ptr(faces), _ptr(keep), _stream(dev))
     _check(lib, rc, "dgs_decimate_apply")
     return vmap, faces, keep.bool()
+
+
+def fill_layout():
+    """(threads per workgroup, items per thread, fixed-point bits of the position, Newell and colour sums, columns of a ring row, taps
+    of the smoothed rim, largest n_rounds) of the dgs_fill_* calls."""
+    return _layout("dgs_fill_layout", 8)
+
+
+def fill_rank(succ, leader, n_rounds, buf_a=None, buf_b=None, rank=None):
+    """dgs_fill_rank -> rank [n] int32 (the position in hole order; -1 where leader is -1) for succ, leader [n] int32.  buf_a, buf_b
+    [n] int64 and rank may be passed in to be reused; after the call the packed entries lie in buf_a (n_rounds even) or buf_b."""
+    lib = load()
+    dev = succ.device
+    n = succ.shape[0]
+    _dec(succ, torch.int32, (n,), "fill_rank: succ"), _dec(leader, torch.int32, (n,), "fill_rank: leader")
+    buf_a = torch.empty(n, dtype=torch.int64, device=dev) if buf_a is None else _dec(buf_a, torch.int64, (n,), "fill_rank: buf_a")
+    buf_b = torch.empty(n, dtype=torch.int64, device=dev) if buf_b is None else _dec(buf_b, torch.int64, (n,), "fill_rank: buf_b")
+    rank = torch.empty(n, dtype=torch.int32, device=dev) if rank is None else _dec(rank, torch.int32, (n,), "fill_rank: rank")
+    if any(t.device != dev for t in (leader, buf_a, buf_b, rank)):
+        raise RuntimeError("fill_rank: every tensor must live on the device of succ")
+    with torch.cuda.device(dev):
+        rc = lib.dgs_fill_rank(n, _ptr(succ), _ptr(leader), int(n_rounds), _ptr(buf_a), _ptr(buf_b), _ptr(rank), _stream(dev))
+    _check(lib, rc, "dgs_fill_rank")
+    return rank
+
+
+def fill_rim(vertices, colors, loop_vertices, rim_loop, loop_offsets, centre, scale):
+    """dgs_fill_rim -> (S [B,3] fp64, SC [B,3] fp64 or None, rows [L,16] int64) for the rims loop_vertices / rim_loop [B] int32,
+    loop_offsets [L+1] int64 of vertices [V,3] (colors [V,3] or None); centre: three Python numbers, scale: a power of two."""
+    lib = load()
+    dev = vertices.device
+    V, B, L = vertices.shape[0], loop_vertices.shape[0], loop_offsets.shape[0] - 1
+    _dec(vertices, torch.float32, (V, 3), "fill_rim: vertices"), _dec(loop_vertices, torch.int32, (B,), "fill_rim: loop_vertices")
+    _dec(rim_loop, torch.int32, (B,), "fill_rim: rim_loop"), _dec(loop_offsets, torch.int64, (L + 1,), "fill_rim: loop_offsets")
+    if colors is not None:
+        _dec(colors, torch.float32, (V, 3), "fill_rim: colors")
+    if any(t is not None and t.device != dev for t in (colors, loop_vertices, rim_loop, loop_offsets)):
+        raise RuntimeError("fill_rim: every tensor must live on the device of vertices")
+    S = torch.empty((B, 3), dtype=torch.float64, device=dev)
+    SC = torch.empty((B, 3), dtype=torch.float64, device=dev) if colors is not None else None
+    rows = torch.empty((L, 16), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.dgs_fill_rim(V, _ptr(vertices), _ptr(colors), B, _ptr(loop_vertices), _ptr(rim_loop), L, _ptr(loop_offsets), float(centre[0]),
+                              float(centre[1]), float(centre[2]), float(scale), _ptr(S), _ptr(SC), _ptr(rows), _stream(dev))
+    _check(lib, rc, "dgs_fill_rim")
+    return S, SC, rows
+
+
+def fill_emit(n_old, lay, loop_vertices, loop_offsets, rows, S, SC, centre, scale, vertices_out, colors_out, faces_out):
+    """dgs_fill_emit for the layout lay (mesh_fill.ring_layout: "rings" [NR,10], "vert_ring" [n_new], "face_ring" [n_new_faces], all
+    int32): writes rows n_old .. n_old + n_new of vertices_out [n_old + n_new,3] fp32 (rows 0 .. n_old hold the input vertices) and of
+    colors_out (or None, with SC None) and all of faces_out [n_new_faces,3] int32."""
+    lib = load()
+    dev = vertices_out.device
+    rings, vert_ring, face_ring = lay["rings"], lay["vert_ring"], lay["face_ring"]
+    NR, NV, NF, B, L = rings.shape[0], vert_ring.shape[0], face_ring.shape[0], loop_vertices.shape[0], loop_offsets.shape[0] - 1
+    n_old = int(n_old)
+    _dec(rings, torch.int32, (NR, fill_layout()[5]), "fill_emit: rings"), _dec(vert_ring, torch.int32, (NV,), "fill_emit: vert_ring")
+    _dec(face_ring, torch.int32, (NF,), "fill_emit: face_ring"), _dec(loop_vertices, torch.int32, (B,), "fill_emit: loop_vertices")
+    _dec(loop_offsets, torch.int64, (L + 1,), "fill_emit: loop_offsets"), _dec(rows, torch.int64, (L, 16), "fill_emit: rows")
+    _dec(S, torch.float64, (B, 3), "fill_emit: S"), _dec(vertices_out, torch.float32, (n_old + NV, 3), "fill_emit: vertices_out")
+    _dec(faces_out, torch.int32, (NF, 3), "fill_emit: faces_out")
+    if (SC is None) != (colors_out is None):
+        raise RuntimeError("fill_emit: SC and colors_out come together")
+    if SC is not None:
+        _dec(SC, torch.float64, (B, 3), "fill_emit: SC"), _dec(colors_out, torch.float32, (n_old + NV, 3), "fill_emit: colors_out")
+    if any(t is not None and t.device != dev for t in (rings, vert_ring, face_ring, loop_vertices, loop_offsets, rows, S, SC, colors_out, faces_out)):
+        raise RuntimeError("fill_emit: every tensor must live on the device of vertices_out")
+    with torch.cuda.device(dev):
+        rc = lib.dgs_fill_emit(n_old, NV, _ptr(vert_ring), NF, _ptr(face_ring), NR, _ptr(rings), L, _ptr(loop_offsets), B, _ptr(loop_vertices),
+                               _ptr(rows), _ptr(S), _ptr(SC), float(centre[0]), float(centre[1]), float(centre[2]), float(scale),
+                               _ptr(vertices_out), _ptr(colors_out), _ptr(faces_out), _stream(dev))
+    _check(lib, rc, "dgs_fill_emit")
+    return vertices_out, colors_out, faces_out

@@ -332,15 +332,16 @@ def keep_largest_components(vertices, faces, colors=None, n_keep=1000, min_faces
 def extract_meshes(model_path, data_path, times=None, voxel_size=0.004, depth_trunc=6.0, n_keep=1000, out_dir=None, iteration=-1,
                    device="cuda:0", white_background=False, alpha_min=0.5, bounds=None, quantile=0.01, margin=None, view_chunk=32,
                    min_faces=50, rasterizer_cls=None, log=None, simplify_cell=None, smooth_iterations=None, smooth_method="taubin",
-                   decimate_faces=None, decimate_ratio=None):
+                   decimate_faces=None, decimate_ratio=None, fill_holes=None):
     """render_mesh.py:169-219: restore() the checkpoint, take the training cameras of the dataset, and for every time (default: the
     times of the test split) render them all at that time, fuse, extract, filter and write <out_dir>/frame_<i>.ply
     (out_dir default: <model_path>/train/ours_<iteration>).  bounds: (lo, hi) of the volume; default: bounds_from_surfels of the
     deformed surfel positions at that time, margin 10 voxels + the truncation.  simplify_cell: if given, the filtered mesh goes
     through mesh_simplify.simplify_mesh with that cell size before it is written (None: written as extracted).
     smooth_iterations: if given, the filtered mesh first goes through mesh_smooth.smooth_mesh(method=smooth_method) with that many
-    iterations -- before the simplification, whose plane quadrics then see cleaner normals (None: nothing is called).  Returns the
-    list of files written."""
+    iterations -- before the simplification, whose plane quadrics then see cleaner normals (None: nothing is called).
+    fill_holes: if given, mesh_fill.fill_holes(max_hole_edges=fill_holes) closes the holes of the filtered mesh before the smoothing,
+    which then blends the fill into the surface (None: nothing is called).  Returns the list of files written."""
     from . import io as dio
     from .fit import restore
     device = torch.device(device)
@@ -373,6 +374,9 @@ def extract_meshes(model_path, data_path, times=None, voxel_size=0.004, depth_tr
             v, f, c = filter_components(v, f, c, n_keep=n_keep, min_faces=min_faces)
         else:
             v, f, c = keep_largest_components(v, f, c, n_keep=n_keep, min_faces=min_faces)
+        if fill_holes is not None:                       # still where it lies: the cells no view saw, closed before the smoothing blends them
+            from .mesh_fill import fill_holes as fill
+            v, f, c = fill(v, f, c, max_hole_edges=fill_holes)
         if smooth_iterations is not None:                # still where it lies: the voxel staircase goes before the quadrics see it
             from .mesh_smooth import smooth_mesh
             v, f, c = smooth_mesh(v, f, c, method=smooth_method, iterations=smooth_iterations)
@@ -408,11 +412,13 @@ def main(argv=None):
     ap.add_argument("--smooth-method", choices=("simple", "laplacian", "taubin"), default="taubin")
     ap.add_argument("--decimate-faces", type=int, default=None, help="decimate every mesh by edge collapse to this many faces, last (default: no)")
     ap.add_argument("--decimate-ratio", type=float, default=None, help="decimate every mesh by edge collapse to this share of its faces, last (default: no)")
+    ap.add_argument("--fill-holes", type=int, default=None, metavar="N",
+                    help="close every hole of up to N edges after the component filter, before the smoothing (default: no)")
     a = ap.parse_args(argv)
     extract_meshes(a.model, a.data, times=a.times, voxel_size=a.voxel_size, depth_trunc=a.depth_trunc, n_keep=a.num_cluster, out_dir=a.out_dir,
                    iteration=a.iteration, device=a.device, white_background=a.white_background, log=print, simplify_cell=a.simplify_cell,
                    smooth_iterations=a.smooth_iterations, smooth_method=a.smooth_method, decimate_faces=a.decimate_faces,
-                   decimate_ratio=a.decimate_ratio)
+                   decimate_ratio=a.decimate_ratio, fill_holes=a.fill_holes)
 
 
 if __name__ == "__main__":

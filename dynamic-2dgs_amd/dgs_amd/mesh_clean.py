@@ -5,7 +5,7 @@ open3d / trimesh.
   cluster_connected_triangles  <- open3d's TriangleMesh.cluster_connected_triangles (utils/mesh_utils.py:24-45 and
                                   render_mesh_trajectory.py:41-88 are built on it): a cluster per triangle, triangles and area per cluster
   filter_components            <- utils/mesh_utils.py:24-45 post_process_mesh: mesh.keep_largest_components with every step on the device
-  clean_mesh                   <- render_mesh_trajectory.py:41-88 clean_mesh, without its fill_holes (trimesh's; not built)
+  clean_mesh                   <- render_mesh_trajectory.py:41-88 clean_mesh; its fill_holes is dgs_amd.mesh_fill's, off by default
 (Simplification -- open3d's simplify_vertex_clustering -- is dgs_amd.mesh_simplify; it shares the face steps of clean_mesh.)
 
 On a HIP device the components are the union-find kernels of libdgs_mesh_ops.so (dgs_cc_labels, include/dgs_mesh_ops.h); on CPU
@@ -210,16 +210,18 @@ def filter_components(vertices, faces, colors=None, n_keep=1000, min_faces=50, a
 
 
 @torch.no_grad()
-def clean_mesh(vertices, faces, colors=None, min_triangles_connected=-1, adjacency="edge"):
-    """The reference's clean_mesh (render_mesh_trajectory.py:41-88) without fill_holes (trimesh's hole filling is not built), on
-    the tensors' device -> (vertices, faces, colors), colors None if none were given:
+def clean_mesh(vertices, faces, colors=None, min_triangles_connected=-1, adjacency="edge", fill_holes=None):
+    """The reference's clean_mesh (render_mesh_trajectory.py:41-88), on the tensors' device -> (vertices, faces, colors), colors None
+    if none were given.  Without fill_holes (None, the default) it is the reference's without its last step:
       (a) weld vertices with exactly equal coordinates (-0.0 equals 0.0; no tolerance): the first occurrence survives and keeps its
           colour, survivors stay in their original order;
       (b) drop a triangle that repeats an earlier one up to a rotation of its corners (opposite winding is a different triangle):
           the first occurrence survives;
       (c) drop triangles that name a vertex twice;
       (d) if min_triangles_connected > 0, drop the components (by `adjacency`) with fewer faces than that;
-      (e) drop the vertices nothing refers to and renumber.
+      (e) drop the vertices nothing refers to and renumber;
+      (f) if fill_holes is an integer, close every hole of up to that many edges: mesh_fill.fill_holes(max_hole_edges=fill_holes)
+          (fp32 vertices only).  The reference's filler, trimesh's, closes loops of 3 and 4 edges.
     Surviving faces keep their order and winding.  Idempotent."""
     _check_mesh("clean_mesh", vertices, faces, colors)
     V, F, dev = vertices.shape[0], faces.shape[0], vertices.device
@@ -238,7 +240,11 @@ def clean_mesh(vertices, faces, colors=None, min_triangles_connected=-1, adjacen
         label = _face_labels(V, f, adjacency)
         counts = _label_counts(label, V if adjacency == "vertex" else f.shape[0])[0]
         f = f[counts[label] >= int(min_triangles_connected)]
-    return _compact(vertices, f.to(faces.dtype), colors, torch.ones(f.shape[0], dtype=torch.bool, device=dev))   # (e)
+    out = _compact(vertices, f.to(faces.dtype), colors, torch.ones(f.shape[0], dtype=torch.bool, device=dev))   # (e)
+    if fill_holes is None:
+        return out
+    from .mesh_fill import fill_holes as fill                 # (f); (mesh_fill imports this module)
+    return fill(*out, max_hole_edges=fill_holes)
 
 
 # ---- shell ----------------------------------------------------------------------------------------------------------------------
@@ -247,7 +253,7 @@ def main(argv=None):
     import os
     from . import io as dio
     ap = argparse.ArgumentParser(prog="python -m dgs_amd.mesh_clean",
-                                 description="Weld and clean a triangle mesh (the reference's clean_mesh without fill_holes); optionally keep its largest components.")
+                                 description="Weld and clean a triangle mesh (the reference's clean_mesh; holes: python -m dgs_amd.mesh_fill); optionally keep its largest components.")
     ap.add_argument("input", help=".ply or .obj")
     ap.add_argument("output", help=".ply")
     ap.add_argument("--min-triangles", type=int, default=-1, help="drop components with fewer faces (default: keep all)")

@@ -3,7 +3,7 @@
  * it, the all-pairs nearest-neighbour and closest-triangle searches behind the geometry metrics of dgs_amd/mesh_metrics.py, the
  * z-buffer triangle rasterizer behind the mesh images of dgs_amd/mesh_render.py, the connected components behind
  * dgs_amd/mesh_clean.py, the quadric vertex clustering behind dgs_amd/mesh_simplify.py, the Laplacian / Taubin steps behind dgs_amd/mesh_smooth.py, and the
- * quadric edge collapse behind dgs_amd/mesh_decimate.py.  The first two replace the PyTorch / open3d path of the reference's render_mesh.py:
+ * quadric edge collapse behind dgs_amd/mesh_decimate.py and the loop ranking and ring fill behind dgs_amd/mesh_fill.py.  The first two replace the PyTorch / open3d path of the reference's render_mesh.py:
  *
  *   dgs_tsdf_integrate          <-  utils/mesh_utils.py:218-266  compute_sdf_perframe + compute_unbounded_tsdf (inv_contraction=None)
  *   dgs_mt_classify / _emit     <-  utils/mesh_utils.py:158-199 / :268-271  volume.extract_triangle_mesh() / marching_cubes_with_contraction
@@ -518,6 +518,97 @@ int dgs_decimate_apply(long long n_vertices, float* pos, long long* rows, float*
  *        (-10), the least valence of an interior opposite vertex, the fixed-point bits of mean_len}: a workgroup takes out[0] * out[1]
  *        faces, edges or vertices. */
 int dgs_decimate_layout(int out[8]);
+
+/* Mesh hole filling: the list ranking behind dgs_amd/mesh_fill.py: boundary_loops and the loop sums, smoothed rims and ring emission
+ * behind fill_holes (the role trimesh's fill_holes has at the end of the reference's clean_mesh, render_mesh_trajectory.py:41-88 --
+ * which closes 3- and 4-edge loops only; this one closes every simple loop up to a size the caller chooses).  Version 2 libraries
+ * from this commit on also carry the dgs_fill_* calls; the version number is unchanged because nothing that existed before changes
+ * (the precedent of dgs_tri_*).  THE STATEMENT -- every fp operation rounded on its own (-ffp-contract=off), fp64 unless it says
+ * otherwise; rn() is round-to-nearest-even to an integer; an int64 is converted to fp64 by one rounding; dgs_amd/mesh_fill.py states
+ * the same arithmetic in PyTorch and CPU tensors run it: the results are bit-identical.
+ *
+ * 1. LOOPS (the wrapper: one sort of packed 64-bit keys, run lengths and prefix sums on the tensors' device; dgs_cc_labels).  Faces
+ *    that name a vertex twice take no part.  A half-edge (a -> b) is a BOUNDARY half-edge when the undirected edge {a, b} occurs
+ *    exactly once among all half-edges; a vertex is SIMPLE when exactly one boundary half-edge leaves it and exactly one enters it; a
+ *    HOLE is a closed cycle of boundary half-edges over simple vertices (a cycle through a bow-tie vertex and an open chain are not).
+ *    The boundary half-edges are the NODES, numbered in ascending order of their tail vertex; succ[h] is the node whose tail is the
+ *    head of h, if that head is simple.  dgs_cc_labels on the pairs (h, succ[h]) gives every node the smallest node of its list --
+ *    of a cycle, the half-edge that leaves its smallest vertex: the LEADER.  A list is a cycle iff every node of it has a successor.
+ * 2. RANKS (dgs_fill_rank).  leader[h] is the leader of h's cycle if the cycle is to be ranked (closed, 3 <= n <= max_hole_edges),
+ *    else -1.  The cycle is cut in front of its leader and ranked by pointer jumping on packed entries next << 32 | distance:
+ *      init      E[h] = (h, 0) if leader[h] < 0, succ[h] is outside [0, n_nodes) or succ[h] == leader[h] (the end of a list),
+ *                else (succ[h], 1)
+ *      a round   with (x, d) = E[h] and (y, e) = E[x]:  E'[h] = (y, d + e) -- one load gives both; a round reads one buffer and
+ *                writes the other, ONE LAUNCH PER ROUND, n_rounds of them; an end (x == h, d == 0) stays what it is
+ *      ranks     rank[h] = -1 if leader[h] < 0, 0 if h == leader[h], else distance + 1
+ *    n_rounds = ceil(log2(longest ranked cycle)) is the caller's: after r rounds a node has jumped min(2^r, its distance to the end).
+ *    rank is the position in HOLE ORDER, the reverse of the boundary direction, starting at the cycle's smallest vertex: a filler
+ *    triangle (r_i, r_i+1, x) then has the winding of the mesh.  No kernel waits for another workgroup and none walks a list: a
+ *    malformed successor table (a cycle that is never cut, two nodes with one successor) gives wrong ranks after the same n_rounds
+ *    launches, never a hang.  The result lies in buf_a after an even number of rounds and in buf_b after an odd one.
+ * 3. LAYOUT (the wrapper).  The rims of the loops to fill, concatenated in hole order: loop_vertices [B] int32, loop_offsets [L + 1]
+ *    int64, rim_loop [B] int32 (the loop of every slot).  A loop of n = 3 gets one triangle and no vertex.  Otherwise
+ *    R = max(1, (113 n + 355) / 710) rings (n / 2 pi in integers: rings about one rim edge apart; R = 1 up to n = 9): ring 1 has n
+ *    vertices, ring k (2 <= k < R) has m_k = (n (R - k) + R / 2) / R, ring R is one vertex, the centre; with R = 1 the centre is
+ *    all.  rings [n_rings,10] int32, one row per ring in (loop, k) order: loop, k, R, n, vertices of the ring, id of its first
+ *    vertex, vertices of the ring before it (the rim for k = 1), id of that ring's first vertex (-1: the rim), index of the first
+ *    face of the strip between the two among the new faces, faces of the strip (a loop of 3: one row, no vertex, one face).
+ *    vert_ring [n_new] and face_ring [n_new_faces] int32 name the row of every new vertex and face.  New vertices and faces follow
+ *    the input's, loop by loop, ring by ring, strip by strip.
+ * 4. FRAME.  centre = (min + max) * 0.5 per axis (fp32) and scale = 2^-e as in dgs_decimate (step 0 there);
+ *    P(v) = (fp64(v) - fp64(centre)) * scale, |P_i| <= 1 + 2^-22.  Colours enter as C = fp64(clamp(colour, 0, 1)), a NaN as 0.
+ * 5. RIM (dgs_fill_rim, a thread per rim slot).  With i the slot's index in its loop of n and all indices mod n:
+ *      S_i = sum over d = -4 .. 4, IN THIS ORDER, of w_d P(r_i+d), w = (1, 8, 28, 56, 70, 56, 28, 8, 1) / 256: the rim after four
+ *      passes of the cyclic [1/4 1/2 1/4] filter (acc = w_-4 P; acc = acc + w_-3 P; ...); SC_i the same of C.  The rim itself
+ *      never moves; S only shapes the new rings.
+ *      rows [n_loops,16] int64 (cleared by the call), columns 0..2 sum of rn(P(r_i) 2^30); 3..5 the Newell sum, component a with
+ *      (b, c) the next two axes: sum of rn(((P_b(r_i) - P_b(r_i+1)) * (P_c(r_i) + P_c(r_i+1))) 2^28); 6..8 sum of rn(C(r_i) 2^24).
+ *    Integer sums: their order and grouping cannot change a bit (the kernel sums neighbouring slots of a loop on chip, as
+ *    dgs_simplify_accumulate does).  NO SUM CAN OVERFLOW for n_rim < 2^31: a position term is below 2^30.001, a Newell term below
+ *    (2.000001)^2 2^28 < 2^30.001, a colour term at most 2^24; 2^31 of them stay below 2^62.
+ * 6. VERTICES (dgs_fill_emit, a thread per new vertex).  Vertex j of ring k with m vertices in a loop of n:
+ *      c = fp64(row_a) / (fp64(n) * 2^30) per axis;  u = 1 - fp64(k) / fp64(R)
+ *      i0 = (j n) / m, t = fp64((j n) mod m) / fp64(m);  s = S_i0 + t * (S_i0+1 - S_i0);  y = c + u * (s - c);  ring R: y = c
+ *      vertex = fp32(fp64(centre) + y * (1 / scale));  colour = fp32(cc + u * (sc - cc)) with cc = fp64(row_6+a) / (fp64(n) * 2^24)
+ *      and sc from SC as s from S.
+ * 7. FACES (dgs_fill_emit, a thread per new face, after the vertices).  A loop of 3: (r_0, r_1, r_2).  The strip into ring R (the
+ *    fan): (A_e, A_e+1 mod m, centre) for every edge e of the ring before it (the rim if R = 1).  The strip rim -> ring 1 (R > 1),
+ *    two faces per rim edge i, with q the ring: the quad r_i, r_i+1, q_i+1, q_i is split along r_i - q_i+1 into (r_i, r_i+1, q_i+1),
+ *    (r_i, q_i+1, q_i), or along r_i+1 - q_i into (r_i, r_i+1, q_i), (r_i+1, q_i+1, q_i): with area(a, b, c) = ((b - a) x (c - a)) . N
+ *    on the fp32 output positions converted to fp64, N = fp64 of the Newell sum, the second split is taken iff the smaller of its
+ *    two areas is greater than the smaller of the first's (a tie or a NaN takes the first).  The strip ring k - 1 (A, m vertices)
+ *    -> ring k (B, m' vertices), 2 <= k < R, is the merge of the two sequences by parameter in closed form: outer edge i gives
+ *    (A_i, A_i+1 mod m, B_g), g = ((i + 1) m' - 1) / m; inner edge j gives (A_h, B_j+1 mod m', B_j), h = ((j + 1) m / m') mod m; the
+ *    m outer faces come first.
+ *
+ * Arguments.  All device memory.  succ, leader, rank [n_nodes] int32; buf_a, buf_b [n_nodes] 64-bit words, two different buffers.
+ * vertices [n_vertices,3] fp32, colors likewise or NULL (then SC and colors_out are NULL too); S, SC [n_rim,3] fp64; rows
+ * [n_loops,16] int64; vertices_out [n_old + n_new,3] fp32 whose first n_old rows hold the input vertices (the face kernel reads them)
+ * and colors_out likewise; faces_out [n_new_faces,3] int32.  dgs_fill_rank: n_rounds + 2 launches; dgs_fill_rim: the clear and one
+ * launch; dgs_fill_emit: two launches.
+ * GUARDS.  Every id and offset read from a buffer is range-checked before an address is formed from it: a rim slot whose loop, range
+ * or vertex ids are out of range writes zeros and adds nothing; a new vertex or face whose ring row, loop or index is out of range
+ * is written as zeros; the face (0, 0, 0).  The Python wrapper produces no such input.
+ * Refused with a negative status before any launch: a negative count, a count >= 2^31 (n_old + n_new among them), n_rounds outside
+ * [0, 31], buf_a == buf_b, a null pointer with a non-zero count (colors / SC / colors_out may be null, together), a centre that is
+ * not finite, a scale that is not positive and finite, new vertices or faces without rings, loops or a rim.  A zero count skips
+ * the launches over it. */
+int dgs_fill_rank(long long n_nodes, const int* succ, const int* leader, int n_rounds, unsigned long long* buf_a, unsigned long long* buf_b,
+                  int* rank, void* stream);
+
+int dgs_fill_rim(long long n_vertices, const float* vertices, const float* colors, long long n_rim, const int* loop_vertices,
+                 const int* rim_loop, long long n_loops, const long long* loop_offsets, double centre_x, double centre_y, double centre_z,
+                 double scale, double* S, double* SC, long long* rows, void* stream);
+
+int dgs_fill_emit(long long n_old, long long n_new, const int* vert_ring, long long n_new_faces, const int* face_ring, long long n_rings,
+                  const int* rings, long long n_loops, const long long* loop_offsets, long long n_rim, const int* loop_vertices,
+                  const long long* rows, const double* S, const double* SC, double centre_x, double centre_y, double centre_z, double scale,
+                  float* vertices_out, float* colors_out, int* faces_out, void* stream);
+
+/* out = {threads per workgroup (T: a workgroup takes T nodes, rim slots, vertices or faces), items per thread, the fixed-point bits
+ *        of the position sums, of the Newell sums and of the colour sums, the columns of a ring row, the taps of the smoothed rim,
+ *        the largest n_rounds}. */
+int dgs_fill_layout(int out[8]);
 
 #ifdef __cplusplus
 }
