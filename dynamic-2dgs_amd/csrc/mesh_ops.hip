@@ -5,8 +5,8 @@
 // mesh decimation and the list ranking and ring emission of the mesh hole filling, gfx950.
 // Compiled with -ffp-contract=off: every fp32 operation of the kernels rounds on its own, which is what makes the result equal to
 // the PyTorch statement of the same arithmetic (dgs_amd/mesh.py) instead of close to it.
-// The kernels live in one header per family, included in the order they were written; this file is the C ABI: the argument checks
-// and the launches.
+// The kernels live in one header per family (mesh_common.h holds what two families share); this file is the C ABI: the argument
+// checks and the launches, one section per family in the order of the includes.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,30 +15,64 @@
 #include <string>
 
 #include "../../include/dgs_mesh_ops.h"
+#include "mesh_common.h"
 #include "mesh_fusion_kernels.h"
 #include "mesh_search_kernels.h"
 #include "mesh_raster_kernels.h"
 #include "mesh_cc_kernels.h"
+#include "mesh_simplify_kernels.h"
+#include "mesh_smooth_kernels.h"
+#include "mesh_decimate_kernels.h"
+#include "mesh_fill_kernels.h"
 
 namespace {
+// ---- shared by every family -----------------------------------------------------------------------------------------------------
 thread_local std::string g_err;
 int fail(int code, const std::string& m) { g_err = m; return code; }
-int launched(const char* what) {
+
+// The status of the launches since the last check, named "<entry>" or "<entry> (<stage>)" in the error.
+int launched(const char* entry, const char* stage = nullptr) {
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-2, std::string(what) + ": " + hipGetErrorString(e));
+    if (e == hipSuccess) return 0;
+    return fail(-2, std::string(entry) + (stage ? " (" + std::string(stage) + ")" : std::string()) + ": " + hipGetErrorString(e));
+}
+
+template <class... P, class... A>
+int launch(const char* entry, const char* stage, void (*kernel)(P...), dim3 grid, dim3 block, void* stream, A... args) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, args...);
+    return launched(entry, stage);
+}
+
+// The same where a count may be zero: nothing to do is no launch and no error.
+template <class... P, class... A>
+int launch_if(bool any, const char* entry, const char* stage, void (*kernel)(P...), dim3 grid, dim3 block, void* stream, A... args) {
+    return any ? launch(entry, stage, kernel, grid, block, stream, args...) : 0;
+}
+
+// Every count in [0, 2^31): ids are int32 (`why` says so), and the fixed-point sums are sized for it.
+int check_counts(const char* what, std::initializer_list<long long> counts, const char* why = "ids are int32") {
+    for (long long n : counts) {
+        if (n < 0) return fail(-1, std::string(what) + ": negative count");
+        if (n >= (1LL << 31)) return fail(-1, std::string(what) + ": every count must be below 2^31 (" + why + ")");
+    }
     return 0;
 }
 
-int check_raster(const char* what, int H, int W, long long n_faces, const float* table) {
-    if (H < 1 || W < 1) return fail(-1, std::string(what) + ": H and W must be >= 1");
-    if ((long long)H * W > (1LL << 30)) return fail(-1, std::string(what) + ": image too large (H * W > 2^30)");
-    if (n_faces < 0) return fail(-1, std::string(what) + ": negative n_faces");
-    if (n_faces >= (1LL << 31)) return fail(-1, std::string(what) + ": n_faces must be below 2^31 (the face is the low 32 bits of the packed minimum)");
-    if (n_faces > 0 && !table) return fail(-1, std::string(what) + ": null pointer");
-    if ((size_t)table % 16 != 0) return fail(-1, std::string(what) + ": the table must be 16-byte aligned");
+// A workgroup of 256 threads per 256 items, for a count that passed check_counts: below 2^23 workgroups.
+dim3 blocks_of_256(long long n) { return dim3((unsigned)((n + 255) / 256)); }
+static_assert(SIMP_THREADS * SIMP_ITEMS_PER_THREAD == 256 && SMOOTH_THREADS == 256 && SMOOTH_VERTS_PER_BLOCK == 256 &&
+                  DEC_THREADS * DEC_ITEMS_PER_THREAD == 256 && FILL_THREADS * FILL_ITEMS_PER_THREAD == 256,
+              "blocks_of_256 sizes the grids of these families");
+
+// The *_layout entry points: the compile-time sizes of a family, for the wrappers' defaults and the tests' shapes.
+template <int N>
+int layout(const char* what, int* out, const int (&values)[N]) {
+    if (!out) return fail(-1, std::string(what) + ": null pointer");
+    for (int i = 0; i < N; ++i) out[i] = values[i];
     return 0;
 }
 
+// ---- fusion and marching tetrahedra ---------------------------------------------------------------------------------------------
 int check_grid(int Nx, int Ny, int Nz, const char* what) {
     if (Nx < 2 || Ny < 2 || Nz < 2) return fail(-1, std::string(what) + ": every grid dimension must be >= 2");
     return 0;
@@ -51,14 +85,7 @@ unsigned blocks_for(long long n, long long cap) {
     return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
 }
 
-// The *_layout entry points: the compile-time sizes of a family, for the wrappers' defaults and the tests' shapes.
-template <int N>
-int layout(const char* what, int* out, const int (&values)[N]) {
-    if (!out) return fail(-1, std::string(what) + ": null pointer");
-    for (int i = 0; i < N; ++i) out[i] = values[i];
-    return 0;
-}
-
+// ---- the two searches -----------------------------------------------------------------------------------------------------------
 // dgs_nn_search and dgs_tri_search differ by these nouns and sizes and by the kernel they launch; search() is everything else.
 struct Search {
     const char *what, *empty, *count, *item, *chunk;   // entry point; refusal of an empty set; names of n_*, the low word, *_chunk
@@ -68,7 +95,7 @@ struct Search {
 
 template <class Launch>
 int search(const Search& s, long long n_query, const float* query, long long n_set, const float* set, long long chunk, unsigned long long* best,
-           void* stream, Launch launch) {
+           void* stream, Launch launch_kernel) {
     const std::string w = s.what;
     if (n_query < 0) return fail(-1, w + ": negative n_query");
     if (n_set < 1) return fail(-1, w + ": " + s.empty);
@@ -83,27 +110,29 @@ int search(const Search& s, long long n_query, const float* query, long long n_s
     if (blocks > 0x7FFFFFFFLL) return fail(-1, w + ": too many queries for one launch");
     hipError_t e = hipMemsetAsync(best, 0xFF, (size_t)n_query * sizeof(unsigned long long), (hipStream_t)stream);
     if (e != hipSuccess) return fail(-2, w + " (init): " + hipGetErrorString(e));
-    launch(dim3((unsigned)blocks, (unsigned)slices), chunk);
-    return launched(s.what);
+    return launch_kernel(dim3((unsigned)blocks, (unsigned)slices), chunk);
 }
 
-// One step of dgs_smooth_steps for a compile-time channel count.
-template <int C>
-void smooth_launch(dim3 grid, hipStream_t st, long long n_vertices, const long long* offsets, const int* neighbours, long long n_entries, int mode,
-                   float s, const unsigned char* pinned, const float* in, float* out) {
-    hipLaunchKernelGGL(smooth_step_kernel<C>, grid, dim3(SMOOTH_THREADS), 0, st, n_vertices, offsets, neighbours, n_entries, mode, s, pinned, in, out);
-}
-
-// The dgs_decimate_* calls: every count in [0, 2^31) (ids are int32, and the quadric sums are sized for it) ...
-int dec_counts(const char* what, std::initializer_list<long long> counts) {
-    for (long long n : counts) {
-        if (n < 0) return fail(-1, std::string(what) + ": negative count");
-        if (n >= (1LL << 31)) return fail(-1, std::string(what) + ": every count must be below 2^31 (ids are int32)");
-    }
+// ---- triangle rasterizer --------------------------------------------------------------------------------------------------------
+int check_raster(const char* what, int H, int W, long long n_faces, const float* table) {
+    if (H < 1 || W < 1) return fail(-1, std::string(what) + ": H and W must be >= 1");
+    if ((long long)H * W > (1LL << 30)) return fail(-1, std::string(what) + ": image too large (H * W > 2^30)");
+    if (n_faces < 0) return fail(-1, std::string(what) + ": negative n_faces");
+    if (n_faces >= (1LL << 31)) return fail(-1, std::string(what) + ": n_faces must be below 2^31 (the face is the low 32 bits of the packed minimum)");
+    if (n_faces > 0 && !table) return fail(-1, std::string(what) + ": null pointer");
+    if ((size_t)table % 16 != 0) return fail(-1, std::string(what) + ": the table must be 16-byte aligned");
     return 0;
 }
 
-// ... and q_bits in [1, Q_MAX] with n_faces * 2^q_bits <= 2^Q_BUDGET: the overflow bound of include/dgs_mesh_ops.h.
+// ---- smoothing ------------------------------------------------------------------------------------------------------------------
+// The step kernel of dgs_smooth_steps for every channel count C in [1, SMOOTH_MAX_C], at index C - 1.
+using SmoothKernel = decltype(&smooth_step_kernel<1>);
+const SmoothKernel smooth_kernels[] = {smooth_step_kernel<1>, smooth_step_kernel<2>, smooth_step_kernel<3>, smooth_step_kernel<4>,
+                                       smooth_step_kernel<5>, smooth_step_kernel<6>, smooth_step_kernel<7>, smooth_step_kernel<8>};
+static_assert(sizeof(smooth_kernels) / sizeof(smooth_kernels[0]) == SMOOTH_MAX_C, "one instantiation per channel count");
+
+// ---- decimation -----------------------------------------------------------------------------------------------------------------
+// q_bits in [1, Q_MAX] with n_faces * 2^q_bits <= 2^Q_BUDGET: the overflow bound of include/dgs_mesh_ops.h.
 int dec_bits(const char* what, int q_bits, long long n_faces) {
     if (q_bits < 1 || q_bits > DEC_Q_MAX || (n_faces > 0 && n_faces > (1LL << (DEC_Q_BUDGET - q_bits))))
         return fail(-1, std::string(what) + ": q_bits must be in [1, " + std::to_string(DEC_Q_MAX) + "] with n_faces * 2^q_bits <= 2^" +
@@ -111,8 +140,7 @@ int dec_bits(const char* what, int q_bits, long long n_faces) {
     return 0;
 }
 
-dim3 dec_blocks(long long n) { return dim3((unsigned)((n + DEC_THREADS - 1) / DEC_THREADS)); }      // n < 2^31: below 2^23 workgroups
-
+// ---- hole filling ---------------------------------------------------------------------------------------------------------------
 // The frame of dgs_fill_rim and dgs_fill_emit: positions enter the sums as (v - centre) * scale, scale a power of two.
 int fill_frame(const char* what, double cx, double cy, double cz, double scale, FillFrame& fr) {
     if (!std::isfinite(cx) || !std::isfinite(cy) || !std::isfinite(cz) || !(scale > 0.0) || !std::isfinite(scale) || !std::isfinite(1.0 / scale))
@@ -127,6 +155,7 @@ extern "C" {
 int dgs_mesh_ops_abi_version(void) { return DGS_MESH_OPS_ABI_VERSION; }
 const char* dgs_mesh_ops_last_error(void) { return g_err.c_str(); }
 
+// ---- fusion and marching tetrahedra (mesh_fusion_kernels.h) ----------------------------------------------------------------------
 int dgs_tsdf_integrate(int Nx, int Ny, int Nz, float ox, float oy, float oz, float voxel, int V, int H, int W, const float* depth,
                        const float* rgb, const float* proj, float trunc, float depth_trunc, float prior_weight, int accumulate, float* tsdf,
                        float* weight, float* color, void* stream) {
@@ -137,46 +166,45 @@ int dgs_tsdf_integrate(int Nx, int Ny, int Nz, float ox, float oy, float oz, flo
     if (!tsdf || !weight || !color || (V > 0 && (!depth || !rgb || !proj))) return fail(-1, "dgs_tsdf_integrate: null pointer");
     const dim3 grid((Nz + BZ - 1) / BZ, (Ny + BY - 1) / BY, (Nx + RX - 1) / RX);
     if (grid.y > 65535u || grid.z > 65535u) return fail(-1, "dgs_tsdf_integrate: grid too large");
-    hipLaunchKernelGGL(tsdf_integrate_kernel, grid, dim3(BZ, BY, 1), 0, (hipStream_t)stream, Nx, Ny, Nz, ox, oy, oz, voxel, V, H, W, depth, rgb,
-                       proj, trunc, depth_trunc, prior_weight, accumulate, tsdf, weight, color);
-    return launched("dgs_tsdf_integrate");
+    return launch("dgs_tsdf_integrate", nullptr, tsdf_integrate_kernel, grid, dim3(BZ, BY, 1), stream, Nx, Ny, Nz, ox, oy, oz, voxel, V, H, W, depth,
+                  rgb, proj, trunc, depth_trunc, prior_weight, accumulate, tsdf, weight, color);
 }
 
 int dgs_mt_classify(int Nx, int Ny, int Nz, const float* tsdf, const float* weight, int* cell_tris, int* point_verts,
                     unsigned char* point_mask, void* stream) {
-    if (int rc = check_grid(Nx, Ny, Nz, "dgs_mt_classify")) return rc;
+    const char* w = "dgs_mt_classify";
+    if (int rc = check_grid(Nx, Ny, Nz, w)) return rc;
     if (!tsdf || !weight || !cell_tris || !point_verts || !point_mask) return fail(-1, "dgs_mt_classify: null pointer");
     const Grid g = make_grid(Nx, Ny, Nz);
     const long long n = (long long)Nx * Ny * Nz;
-    const unsigned nb = blocks_for(n, 1 << 20);
-    hipLaunchKernelGGL(mt_cells_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, g, n, tsdf, weight, cell_tris);
-    if (int rc = launched("dgs_mt_classify (cells)")) return rc;
-    hipLaunchKernelGGL(mt_points_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, g, n, tsdf, cell_tris, point_verts, point_mask);
-    return launched("dgs_mt_classify (points)");
+    const dim3 grid(blocks_for(n, 1 << 20));
+    if (int rc = launch(w, "cells", mt_cells_kernel, grid, dim3(256), stream, g, n, tsdf, weight, cell_tris)) return rc;
+    return launch(w, "points", mt_points_kernel, grid, dim3(256), stream, g, n, tsdf, cell_tris, point_verts, point_mask);
 }
 
 int dgs_mt_emit(int Nx, int Ny, int Nz, float ox, float oy, float oz, float voxel, const float* tsdf, const float* color, long long n_cells,
                 const long long* cells, const int* cell_tris, const long long* tri_incl, long long n_points, const long long* points,
                 const unsigned char* point_mask, const long long* vert_incl, float* vertices, float* vertex_colors, int* faces, void* stream) {
-    if (int rc = check_grid(Nx, Ny, Nz, "dgs_mt_emit")) return rc;
+    const char* w = "dgs_mt_emit";
+    if (int rc = check_grid(Nx, Ny, Nz, w)) return rc;
     if (n_cells < 0 || n_points < 0) return fail(-1, "dgs_mt_emit: negative count");
     if (n_cells == 0 || n_points == 0) return 0;
     if (!tsdf || !cells || !cell_tris || !tri_incl || !points || !point_mask || !vert_incl || !vertices || !faces || (color && !vertex_colors))
         return fail(-1, "dgs_mt_emit: null pointer");
     const Grid g = make_grid(Nx, Ny, Nz);
-    hipLaunchKernelGGL(mt_vertices_kernel, dim3(blocks_for(n_points, 1LL << 31)), dim3(256), 0, (hipStream_t)stream, g, ox, oy, oz, voxel, tsdf, color,
-                       n_points, points, point_mask, vert_incl, vertices, vertex_colors);
-    if (int rc = launched("dgs_mt_emit (vertices)")) return rc;
-    hipLaunchKernelGGL(mt_faces_kernel, dim3(blocks_for(n_cells, 1LL << 31)), dim3(256), 0, (hipStream_t)stream, g, tsdf, n_cells, cells, cell_tris,
-                       tri_incl, point_mask, vert_incl, faces);
-    return launched("dgs_mt_emit (faces)");
+    if (int rc = launch(w, "vertices", mt_vertices_kernel, dim3(blocks_for(n_points, 1LL << 31)), dim3(256), stream, g, ox, oy, oz, voxel, tsdf, color,
+                        n_points, points, point_mask, vert_incl, vertices, vertex_colors))
+        return rc;
+    return launch(w, "faces", mt_faces_kernel, dim3(blocks_for(n_cells, 1LL << 31)), dim3(256), stream, g, tsdf, n_cells, cells, cell_tris, tri_incl,
+                  point_mask, vert_incl, faces);
 }
 
+// ---- the two searches and the earth mover's distance (mesh_search_kernels.h) -----------------------------------------------------
 int dgs_nn_search(long long n_query, const float* query, long long n_ref, const float* ref, long long ref_chunk, unsigned long long* best,
                   void* stream) {
     const Search s{"dgs_nn_search", "the reference set must hold at least one point (n_ref >= 1)", "n_ref", "index", "ref_chunk", NN_Q, 1};
     return search(s, n_query, query, n_ref, ref, ref_chunk, best, stream, [&](dim3 grid, long long chunk) {
-        hipLaunchKernelGGL(nn_search_kernel, grid, dim3(NN_THREADS), 0, (hipStream_t)stream, n_query, query, n_ref, ref, chunk, best);
+        return launch(s.what, nullptr, nn_search_kernel, grid, dim3(NN_THREADS), stream, n_query, query, n_ref, ref, chunk, best);
     });
 }
 
@@ -186,8 +214,8 @@ int dgs_tri_search(long long n_query, const float* query, long long n_tri, const
                    void* stream) {
     const Search s{"dgs_tri_search", "the table must hold at least one triangle (n_tri >= 1)", "n_tri", "face", "tri_chunk", TRI_Q, 16};
     return search(s, n_query, query, n_tri, table, tri_chunk, best, stream, [&](dim3 grid, long long chunk) {
-        hipLaunchKernelGGL(tri_search_kernel, grid, dim3(TRI_THREADS), 0, (hipStream_t)stream, n_query, query, n_tri,
-                           reinterpret_cast<const float4*>(table), chunk, best);
+        return launch(s.what, nullptr, tri_search_kernel, grid, dim3(TRI_THREADS), stream, n_query, query, n_tri,
+                      reinterpret_cast<const float4*>(table), chunk, best);
     });
 }
 
@@ -242,8 +270,7 @@ int dgs_emd_auction(long long n, const float* a, const float* b, float inv_q, lo
     const dim3 threads(EMD_THREADS);
     const unsigned per_point = (unsigned)((n + EMD_THREADS - 1) / EMD_THREADS);
     const unsigned per_wave = (unsigned)std::min<long long>((n + EMD_WAVES - 1) / EMD_WAVES, EMD_MAX_BLOCKS);
-    hipLaunchKernelGGL(emd_max_cost_kernel, dim3(per_wave), threads, 0, st, s);
-    if (int rc = launched("dgs_emd_auction (max cost)")) return rc;
+    if (int rc = launch("dgs_emd_auction", "max cost", emd_max_cost_kernel, dim3(per_wave), threads, stream, s)) return rc;
     if (read_ctrl() != hipSuccess) return hip_failed("max cost");
     long long eps = std::max<long long>(1, h.max_cost / 2), rounds = 0;
     int phase = 0;
@@ -268,7 +295,7 @@ int dgs_emd_auction(long long n, const float* a, const float* b, float inv_q, lo
                     hipLaunchKernelGGL(emd_bid_sparse_kernel, bid_grid, threads, 0, st, s, cur, eps);
                 hipLaunchKernelGGL(emd_resolve_kernel, resolve_grid, threads, 0, st, s, cur);
             }
-            if (int rc = launched("dgs_emd_auction (round)")) return rc;
+            if (int rc = launched("dgs_emd_auction", "round")) return rc;
             if (read_ctrl() != hipSuccess) return hip_failed("round");
             if (h.status != 0) return fail(-4, w + ": a bid of phase " + std::to_string(phase) + " does not fit 39 bits");
             bidders = h.count[cur], rounds = h.rounds;
@@ -278,8 +305,7 @@ int dgs_emd_auction(long long n, const float* a, const float* b, float inv_q, lo
     }
     if ((e = hipMemsetAsync(assignment, 0xFF, (size_t)n * sizeof(int), st)) != hipSuccess) return hip_failed("assignment");
     hipLaunchKernelGGL(emd_assign_kernel, dim3(per_point), threads, 0, st, s);
-    hipLaunchKernelGGL(emd_sums_kernel, dim3(per_wave), threads, 0, st, s);
-    if (int rc = launched("dgs_emd_auction (sums)")) return rc;
+    if (int rc = launch("dgs_emd_auction", "sums", emd_sums_kernel, dim3(per_wave), threads, stream, s)) return rc;
     if (read_ctrl() != hipSuccess) return hip_failed("sums");
     if (h.status != 0) return fail(-5, w + ": the owners are not a permutation at the end");
     result[0] = h.primal, result[1] = h.sum_min - h.sum_price, result[2] = h.rounds, result[3] = h.max_cost, result[4] = phase + 1, result[5] = eps;
@@ -290,9 +316,11 @@ int dgs_emd_layout(int out[6]) {
     return layout("dgs_emd_layout", out, {EMD_THREADS, EMD_T, EMD_SPARSE_MAX, EMD_RESULTS, EMD_SCRATCH_FIXED, EMD_SCRATCH_PER_POINT});
 }
 
+// ---- triangle rasterizer (mesh_raster_kernels.h) ---------------------------------------------------------------------------------
 int dgs_mesh_raster(long long n_faces, const float* table, const int* list, long long n_list, int path, int H, int W,
                     unsigned long long* best, int clear, void* stream) {
-    if (int rc = check_raster("dgs_mesh_raster", H, W, n_faces, table)) return rc;
+    const char* w = "dgs_mesh_raster";
+    if (int rc = check_raster(w, H, W, n_faces, table)) return rc;
     if (n_list < 0) return fail(-1, "dgs_mesh_raster: negative n_list");
     if (n_list >= (1LL << 31)) return fail(-1, "dgs_mesh_raster: n_list must be below 2^31");
     if (path != 0 && path != 1) return fail(-1, "dgs_mesh_raster: path must be 0 (small boxes) or 1 (large boxes)");
@@ -303,20 +331,17 @@ int dgs_mesh_raster(long long n_faces, const float* table, const int* list, long
     }
     if (n_list == 0 || n_faces == 0) return 0;
     const float4* rows = reinterpret_cast<const float4*>(table);
-    if (path == 0) {
-        hipLaunchKernelGGL(raster_small_kernel, dim3((unsigned)((n_list + RAS_THREADS - 1) / RAS_THREADS)), dim3(RAS_THREADS), 0, (hipStream_t)stream,
-                           n_faces, rows, list, n_list, H, W, best);
-        return launched("dgs_mesh_raster (small)");
-    }
+    if (path == 0)
+        return launch(w, "small", raster_small_kernel, dim3((unsigned)((n_list + RAS_THREADS - 1) / RAS_THREADS)), dim3(RAS_THREADS), stream, n_faces, rows,
+                      list, n_list, H, W, best);
     // few large faces: several workgroups per face, each a stripe of its rows; many: one each.  The result does not depend on it.
     long long stripes = RAS_TARGET_GROUPS / n_list, rows_of_tiles = ((long long)H + RAS_TILE_Y - 1) / RAS_TILE_Y;
     stripes = stripes < 1 ? 1 : (stripes > RAS_MAX_STRIPES ? RAS_MAX_STRIPES : stripes);
     if (stripes > rows_of_tiles) stripes = rows_of_tiles;
     // (a launch of 2^32 threads or more along x is refused: above RAS_MAX_GROUPS faces a workgroup takes several of them in turn)
     const long long groups = n_list < RAS_MAX_GROUPS ? n_list : RAS_MAX_GROUPS;
-    hipLaunchKernelGGL(raster_large_kernel, dim3((unsigned)groups, (unsigned)stripes), dim3(RAS_THREADS), 0, (hipStream_t)stream, n_faces, rows, list,
-                       n_list, H, W, best);
-    return launched("dgs_mesh_raster (large)");
+    return launch(w, "large", raster_large_kernel, dim3((unsigned)groups, (unsigned)stripes), dim3(RAS_THREADS), stream, n_faces, rows, list, n_list, H,
+                  W, best);
 }
 
 int dgs_mesh_resolve(int H, int W, const unsigned long long* best, long long n_faces, const float* table, const int* faces,
@@ -328,15 +353,16 @@ int dgs_mesh_resolve(int H, int W, const unsigned long long* best, long long n_f
     if (!best) return fail(-1, "dgs_mesh_resolve: null pointer");
     if (C > 0 && (!background || !image || (n_faces > 0 && !faces) || (n_vertices > 0 && !attr))) return fail(-1, "dgs_mesh_resolve: null pointer");
     const size_t n = (size_t)H * W;
-    hipLaunchKernelGGL(raster_resolve_kernel, dim3((unsigned)((n + RAS_THREADS - 1) / RAS_THREADS)), dim3(RAS_THREADS), 0, (hipStream_t)stream, H, W, best,
-                       n_faces, reinterpret_cast<const float4*>(table), faces, n_vertices, attr, C, background, face_id, depth, bary,
-                       C > 0 ? image : nullptr);
-    return launched("dgs_mesh_resolve");
+    return launch("dgs_mesh_resolve", nullptr, raster_resolve_kernel, dim3((unsigned)((n + RAS_THREADS - 1) / RAS_THREADS)), dim3(RAS_THREADS), stream, H, W,
+                  best, n_faces, reinterpret_cast<const float4*>(table), faces, n_vertices, attr, C, background, face_id, depth, bary,
+                  C > 0 ? image : nullptr);
 }
 
 int dgs_mesh_raster_layout(int out[4]) { return layout("dgs_mesh_raster_layout", out, {RAS_SMALL_AREA, RAS_THREADS, RAS_ROW, RAS_MAX_C}); }
 
+// ---- connected components (mesh_cc_kernels.h) ------------------------------------------------------------------------------------
 int dgs_cc_labels(long long n_nodes, const int* groups, long long n_groups, int k, int* label, void* stream) {
+    const char* w = "dgs_cc_labels";
     if (k != 2 && k != 3) return fail(-1, "dgs_cc_labels: k must be 2 or 3");
     if (n_nodes < 0 || n_groups < 0) return fail(-1, "dgs_cc_labels: negative count");
     if (n_nodes >= (1LL << 31)) return fail(-1, "dgs_cc_labels: n_nodes must be below 2^31 (labels are int32)");
@@ -344,44 +370,32 @@ int dgs_cc_labels(long long n_nodes, const int* groups, long long n_groups, int 
     if (n_nodes == 0) return 0;
     const long long per_block = (long long)CC_THREADS * CC_GROUPS_PER_THREAD;
     auto blocks = [&](long long n) { const long long b = (n + per_block - 1) / per_block; return dim3((unsigned)(b > CC_MAX_BLOCKS ? CC_MAX_BLOCKS : b)); };
-    hipLaunchKernelGGL(cc_init_kernel, blocks(n_nodes), dim3(CC_THREADS), 0, (hipStream_t)stream, n_nodes, label);
-    if (int rc = launched("dgs_cc_labels (init)")) return rc;
+    if (int rc = launch(w, "init", cc_init_kernel, blocks(n_nodes), dim3(CC_THREADS), stream, n_nodes, label)) return rc;
     if (n_groups == 0) return 0;
-    if (k == 2)
-        hipLaunchKernelGGL(cc_hook_kernel<2>, blocks(n_groups), dim3(CC_THREADS), 0, (hipStream_t)stream, n_nodes, groups, n_groups, label);
-    else
-        hipLaunchKernelGGL(cc_hook_kernel<3>, blocks(n_groups), dim3(CC_THREADS), 0, (hipStream_t)stream, n_nodes, groups, n_groups, label);
-    if (int rc = launched("dgs_cc_labels (hook)")) return rc;
-    hipLaunchKernelGGL(cc_compress_kernel, blocks(n_nodes), dim3(CC_THREADS), 0, (hipStream_t)stream, n_nodes, label);
-    return launched("dgs_cc_labels (compress)");
+    decltype(&cc_hook_kernel<2>) hook = cc_hook_kernel<2>;
+    if (k == 3) hook = cc_hook_kernel<3>;
+    if (int rc = launch(w, "hook", hook, blocks(n_groups), dim3(CC_THREADS), stream, n_nodes, groups, n_groups, label)) return rc;
+    return launch(w, "compress", cc_compress_kernel, blocks(n_nodes), dim3(CC_THREADS), stream, n_nodes, label);
 }
 
 int dgs_cc_layout(int out[2]) { return layout("dgs_cc_layout", out, {CC_THREADS, CC_GROUPS_PER_THREAD}); }
 
+// ---- simplification (mesh_simplify_kernels.h) ------------------------------------------------------------------------------------
 int dgs_simplify_accumulate(long long n_vertices, const float* vertices, const float* colors, long long n_faces, const int* faces,
                             const int* cluster, long long n_clusters, const float* centres, float cell, long long* rows, void* stream) {
-    if (n_vertices < 0 || n_faces < 0 || n_clusters < 0) return fail(-1, "dgs_simplify_accumulate: negative count");
-    if (n_vertices >= (1LL << 31) || n_faces >= (1LL << 31) || n_clusters >= (1LL << 31))
-        return fail(-1, "dgs_simplify_accumulate: every count must be below 2^31 (ids are int32, and the sums are sized for it)");
+    const char* w = "dgs_simplify_accumulate";
+    if (int rc = check_counts(w, {n_vertices, n_faces, n_clusters}, "ids are int32, and the sums are sized for it")) return rc;
     if (!(cell > 0.0f) || !std::isfinite(cell)) return fail(-1, "dgs_simplify_accumulate: cell must be positive and finite");
     if ((n_clusters > 0 && (!rows || !centres)) || (n_vertices > 0 && (!vertices || !cluster)) || (n_faces > 0 && (!faces || !vertices || !cluster)))
         return fail(-1, "dgs_simplify_accumulate: null pointer");
     if (n_clusters == 0) return 0;
-    hipError_t e = hipMemsetAsync(rows, 0, (size_t)n_clusters * SIMP_ROW * sizeof(long long), (hipStream_t)stream);
+    hipError_t e = hipMemsetAsync(rows, 0, (size_t)n_clusters * SUM_ROW * sizeof(long long), (hipStream_t)stream);
     if (e != hipSuccess) return fail(-2, std::string("dgs_simplify_accumulate (clear): ") + hipGetErrorString(e));
-    const long long per_block = (long long)SIMP_THREADS * SIMP_ITEMS_PER_THREAD;
-    auto blocks = [&](long long n) { return dim3((unsigned)((n + per_block - 1) / per_block)); };       // n < 2^31: below 2^23 workgroups
-    if (n_vertices > 0) {
-        hipLaunchKernelGGL(simp_vertex_kernel, blocks(n_vertices), dim3(SIMP_THREADS), 0, (hipStream_t)stream, n_vertices, vertices, colors, cluster,
-                           n_clusters, centres, cell, rows);
-        if (int rc = launched("dgs_simplify_accumulate (vertices)")) return rc;
-    }
-    if (n_faces > 0 && n_vertices > 0) {
-        hipLaunchKernelGGL(simp_face_kernel, blocks(n_faces), dim3(SIMP_THREADS), 0, (hipStream_t)stream, n_faces, faces, n_vertices, vertices, cluster,
-                           n_clusters, centres, cell, rows);
-        if (int rc = launched("dgs_simplify_accumulate (faces)")) return rc;
-    }
-    return 0;
+    if (int rc = launch_if(n_vertices > 0, w, "vertices", simp_vertex_kernel, blocks_of_256(n_vertices), dim3(SIMP_THREADS), stream, n_vertices,
+                           vertices, colors, cluster, n_clusters, centres, cell, rows))
+        return rc;
+    return launch_if(n_faces > 0 && n_vertices > 0, w, "faces", simp_face_kernel, blocks_of_256(n_faces), dim3(SIMP_THREADS), stream, n_faces,
+                     faces, n_vertices, vertices, cluster, n_clusters, centres, cell, rows);
 }
 
 int dgs_simplify_solve(long long n_clusters, const long long* rows, const float* centres, float cell, int placement, float* vertices,
@@ -392,19 +406,18 @@ int dgs_simplify_solve(long long n_clusters, const long long* rows, const float*
     if (!(cell > 0.0f) || !std::isfinite(cell)) return fail(-1, "dgs_simplify_solve: cell must be positive and finite");
     if (n_clusters > 0 && (!rows || !centres || !vertices)) return fail(-1, "dgs_simplify_solve: null pointer");
     if (n_clusters == 0) return 0;
-    hipLaunchKernelGGL(simp_solve_kernel, dim3((unsigned)((n_clusters + SIMP_THREADS - 1) / SIMP_THREADS)), dim3(SIMP_THREADS), 0, (hipStream_t)stream,
-                       n_clusters, rows, centres, cell, placement, vertices, colors);
-    return launched("dgs_simplify_solve");
+    return launch("dgs_simplify_solve", nullptr, simp_solve_kernel, blocks_of_256(n_clusters), dim3(SIMP_THREADS), stream, n_clusters, rows, centres, cell,
+                  placement, vertices, colors);
 }
 
 int dgs_simplify_layout(int out[5]) {
     return layout("dgs_simplify_layout", out, {SIMP_THREADS, SIMP_ITEMS_PER_THREAD, SIMP_Q, SIMP_W_MAX, SIMP_LAMBDA_EXP});
 }
 
+// ---- smoothing (mesh_smooth_kernels.h) -------------------------------------------------------------------------------------------
 int dgs_smooth_steps(long long n_vertices, const long long* offsets, const int* neighbours, long long n_entries, int C, int mode,
                      const float* factors, int n_steps, const unsigned char* pinned, float* x, float* tmp, void* stream) {
-    if (n_vertices < 0 || n_entries < 0 || n_steps < 0) return fail(-1, "dgs_smooth_steps: negative count");
-    if (n_vertices >= (1LL << 31) || n_entries >= (1LL << 31)) return fail(-1, "dgs_smooth_steps: every count must be below 2^31 (ids are int32)");
+    if (int rc = check_counts("dgs_smooth_steps", {n_vertices, n_entries, n_steps})) return rc;
     if (C < 1 || C > SMOOTH_MAX_C) return fail(-1, "dgs_smooth_steps: C must be in [1, " + std::to_string(SMOOTH_MAX_C) + "]");
     if (mode != 0 && mode != 1) return fail(-1, "dgs_smooth_steps: mode must be 0 (laplacian) or 1 (simple)");
     if (n_steps > SMOOTH_MAX_STEPS) return fail(-1, "dgs_smooth_steps: n_steps must be at most " + std::to_string(SMOOTH_MAX_STEPS) + " (dgs_smooth_layout)");
@@ -413,26 +426,16 @@ int dgs_smooth_steps(long long n_vertices, const long long* offsets, const int* 
     for (int k = 0; k < n_steps; ++k)
         if (!std::isfinite(factors[k])) return fail(-1, "dgs_smooth_steps: factor " + std::to_string(k) + " is not finite");
     if (n_steps == 0 || n_vertices == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)((n_vertices + SMOOTH_VERTS_PER_BLOCK - 1) / SMOOTH_VERTS_PER_BLOCK));     // n_vertices < 2^31: below 2^23 workgroups
+    const SmoothKernel kernel = smooth_kernels[C - 1];
     float *src = x, *dst = tmp;
     for (int k = 0; k < n_steps; ++k) {
-        const float s = factors[k];
-        switch (C) {
-            case 1: smooth_launch<1>(grid, st, n_vertices, offsets, neighbours, n_entries, mode, s, pinned, src, dst); break;
-            case 2: smooth_launch<2>(grid, st, n_vertices, offsets, neighbours, n_entries, mode, s, pinned, src, dst); break;
-            case 3: smooth_launch<3>(grid, st, n_vertices, offsets, neighbours, n_entries, mode, s, pinned, src, dst); break;
-            case 4: smooth_launch<4>(grid, st, n_vertices, offsets, neighbours, n_entries, mode, s, pinned, src, dst); break;
-            case 5: smooth_launch<5>(grid, st, n_vertices, offsets, neighbours, n_entries, mode, s, pinned, src, dst); break;
-            case 6: smooth_launch<6>(grid, st, n_vertices, offsets, neighbours, n_entries, mode, s, pinned, src, dst); break;
-            case 7: smooth_launch<7>(grid, st, n_vertices, offsets, neighbours, n_entries, mode, s, pinned, src, dst); break;
-            default: smooth_launch<8>(grid, st, n_vertices, offsets, neighbours, n_entries, mode, s, pinned, src, dst); break;
-        }
-        if (int rc = launched("dgs_smooth_steps")) return rc;
+        if (int rc = launch("dgs_smooth_steps", nullptr, kernel, blocks_of_256(n_vertices), dim3(SMOOTH_THREADS), stream, n_vertices, offsets, neighbours,
+                            n_entries, mode, factors[k], pinned, src, dst))
+            return rc;
         std::swap(src, dst);
     }
     if (src != x) {                                                        // an odd count left the result in tmp
-        hipError_t e = hipMemcpyAsync(x, tmp, (size_t)n_vertices * C * sizeof(float), hipMemcpyDeviceToDevice, st);
+        hipError_t e = hipMemcpyAsync(x, tmp, (size_t)n_vertices * C * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream);
         if (e != hipSuccess) return fail(-2, std::string("dgs_smooth_steps (copy): ") + hipGetErrorString(e));
     }
     return 0;
@@ -442,85 +445,74 @@ int dgs_smooth_layout(int out[4]) {
     return layout("dgs_smooth_layout", out, {SMOOTH_THREADS, SMOOTH_VERTS_PER_BLOCK, SMOOTH_MAX_C, SMOOTH_MAX_STEPS});
 }
 
+// ---- decimation (mesh_decimate_kernels.h) ----------------------------------------------------------------------------------------
 int dgs_decimate_quadrics(long long n_vertices, const float* pos, long long n_faces, const int* faces, float mean_len, int q_bits,
                           long long* rows, void* stream) {
-    if (int rc = dec_counts("dgs_decimate_quadrics", {n_vertices, n_faces})) return rc;
-    if (int rc = dec_bits("dgs_decimate_quadrics", q_bits, n_faces)) return rc;
+    const char* w = "dgs_decimate_quadrics";
+    if (int rc = check_counts(w, {n_vertices, n_faces})) return rc;
+    if (int rc = dec_bits(w, q_bits, n_faces)) return rc;
     if (!(mean_len > 0.0f) || !std::isfinite(mean_len)) return fail(-1, "dgs_decimate_quadrics: mean_len must be positive and finite");
     if ((n_vertices > 0 && (!pos || !rows)) || (n_faces > 0 && !faces)) return fail(-1, "dgs_decimate_quadrics: null pointer");
     if (n_vertices == 0) return 0;
     hipError_t e = hipMemsetAsync(rows, 0, (size_t)n_vertices * DEC_ROW * sizeof(long long), (hipStream_t)stream);
     if (e != hipSuccess) return fail(-2, std::string("dgs_decimate_quadrics (clear): ") + hipGetErrorString(e));
     if (n_faces == 0) return 0;
-    hipLaunchKernelGGL(dec_quadric_kernel, dec_blocks(n_faces), dim3(DEC_THREADS), 0, (hipStream_t)stream, n_faces, faces, n_vertices, pos, mean_len,
-                       std::ldexp(1.0, q_bits), rows);
-    return launched("dgs_decimate_quadrics");
+    return launch(w, nullptr, dec_quadric_kernel, blocks_of_256(n_faces), dim3(DEC_THREADS), stream, n_faces, faces, n_vertices, pos, mean_len,
+                  std::ldexp(1.0, q_bits), rows);
 }
 
 int dgs_decimate_edges(long long n_vertices, const float* pos, const long long* rows, const unsigned char* flags, long long n_faces,
                        const int* faces, long long n_edges, const int* edges, const long long* adj_offsets, const int* adj, long long n_adj,
                        const long long* vf_offsets, const int* vf, long long n_vf, int q_bits, float max_cost, float* cost, float* place,
                        unsigned char* valid, void* stream) {
-    if (int rc = dec_counts("dgs_decimate_edges", {n_vertices, n_faces, n_edges, n_adj, n_vf})) return rc;
-    if (int rc = dec_bits("dgs_decimate_edges", q_bits, n_faces)) return rc;
+    const char* w = "dgs_decimate_edges";
+    if (int rc = check_counts(w, {n_vertices, n_faces, n_edges, n_adj, n_vf})) return rc;
+    if (int rc = dec_bits(w, q_bits, n_faces)) return rc;
     if (!(max_cost >= 0.0f)) return fail(-1, "dgs_decimate_edges: max_cost must be >= 0 (+inf for no bound)");
     if ((n_vertices > 0 && (!pos || !rows || !flags || !adj_offsets || !vf_offsets)) || (n_faces > 0 && !faces) || (n_adj > 0 && !adj) ||
         (n_vf > 0 && !vf) || (n_edges > 0 && (!edges || !cost || !place || !valid)))
         return fail(-1, "dgs_decimate_edges: null pointer");
     if (n_edges == 0) return 0;
-    hipLaunchKernelGGL(dec_edge_kernel, dec_blocks(n_edges), dim3(DEC_THREADS), 0, (hipStream_t)stream, n_vertices, pos, rows, flags, n_faces, faces,
-                       n_edges, edges, adj_offsets, adj, n_adj, vf_offsets, vf, n_vf, std::ldexp(1.0, -q_bits), max_cost, cost, place, valid);
-    return launched("dgs_decimate_edges");
+    return launch(w, nullptr, dec_edge_kernel, blocks_of_256(n_edges), dim3(DEC_THREADS), stream, n_vertices, pos, rows, flags, n_faces, faces, n_edges,
+                  edges, adj_offsets, adj, n_adj, vf_offsets, vf, n_vf, std::ldexp(1.0, -q_bits), max_cost, cost, place, valid);
 }
 
 int dgs_decimate_select(long long n_vertices, long long n_edges, const int* edges, const float* cost, const unsigned char* compete,
                         unsigned long long* m1, unsigned long long* m2, unsigned char* selected, void* stream) {
-    if (int rc = dec_counts("dgs_decimate_select", {n_vertices, n_edges})) return rc;
+    const char* w = "dgs_decimate_select";
+    if (int rc = check_counts(w, {n_vertices, n_edges})) return rc;
     if ((n_vertices > 0 && (!m1 || !m2)) || (n_edges > 0 && (!edges || !cost || !compete || !selected))) return fail(-1, "dgs_decimate_select: null pointer");
-    hipStream_t st = (hipStream_t)stream;
+    const dim3 per_vertex = blocks_of_256(n_vertices), per_edge = blocks_of_256(n_edges), threads(DEC_THREADS);
+    if (int rc = launch_if(n_vertices > 0, w, "init", dec_fill_kernel, per_vertex, threads, stream, n_vertices, m1, DEC_NO_KEY)) return rc;
+    if (int rc = launch_if(n_edges > 0 && n_vertices > 0, w, "pass 1", dec_select_kernel<1>, per_edge, threads, stream, n_vertices, n_edges, edges,
+                           cost, compete, m1, m2, selected))
+        return rc;
     if (n_vertices > 0) {
-        hipLaunchKernelGGL(dec_fill_kernel, dec_blocks(n_vertices), dim3(DEC_THREADS), 0, st, n_vertices, m1, DEC_NO_KEY);
-        if (int rc = launched("dgs_decimate_select (init)")) return rc;
-    }
-    if (n_edges > 0 && n_vertices > 0) {
-        hipLaunchKernelGGL(dec_select_kernel<1>, dec_blocks(n_edges), dim3(DEC_THREADS), 0, st, n_vertices, n_edges, edges, cost, compete, m1, m2, selected);
-        if (int rc = launched("dgs_decimate_select (pass 1)")) return rc;
-    }
-    if (n_vertices > 0) {
-        hipError_t e = hipMemcpyAsync(m2, m1, (size_t)n_vertices * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st);
+        hipError_t e = hipMemcpyAsync(m2, m1, (size_t)n_vertices * sizeof(unsigned long long), hipMemcpyDeviceToDevice, (hipStream_t)stream);
         if (e != hipSuccess) return fail(-2, std::string("dgs_decimate_select (copy): ") + hipGetErrorString(e));
     }
     if (n_edges == 0) return 0;
-    if (n_vertices > 0) {
-        hipLaunchKernelGGL(dec_select_kernel<2>, dec_blocks(n_edges), dim3(DEC_THREADS), 0, st, n_vertices, n_edges, edges, cost, compete, m1, m2, selected);
-        if (int rc = launched("dgs_decimate_select (pass 2)")) return rc;
-    }
-    hipLaunchKernelGGL(dec_select_kernel<3>, dec_blocks(n_edges), dim3(DEC_THREADS), 0, st, n_vertices, n_edges, edges, cost, compete, m1, m2, selected);
-    return launched("dgs_decimate_select (pass 3)");
+    if (int rc = launch_if(n_vertices > 0, w, "pass 2", dec_select_kernel<2>, per_edge, threads, stream, n_vertices, n_edges, edges, cost, compete, m1,
+                           m2, selected))
+        return rc;
+    return launch(w, "pass 3", dec_select_kernel<3>, per_edge, threads, stream, n_vertices, n_edges, edges, cost, compete, m1, m2, selected);
 }
 
 int dgs_decimate_apply(long long n_vertices, float* pos, long long* rows, float* colors, const unsigned char* flags, unsigned char* moved, int* vmap,
                        long long n_edges, const int* edges, const float* place, long long n_sel, const int* sel, long long n_faces, int* faces,
                        unsigned char* keep, void* stream) {
-    if (int rc = dec_counts("dgs_decimate_apply", {n_vertices, n_edges, n_sel, n_faces})) return rc;
+    const char* w = "dgs_decimate_apply";
+    if (int rc = check_counts(w, {n_vertices, n_edges, n_sel, n_faces})) return rc;
     if ((n_vertices > 0 && (!pos || !rows || !flags || !moved || !vmap)) || (n_edges > 0 && (!edges || !place)) || (n_sel > 0 && !sel) ||
         (n_faces > 0 && (!faces || !keep)))
         return fail(-1, "dgs_decimate_apply: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    if (n_vertices > 0) {
-        hipLaunchKernelGGL(dec_iota_kernel, dec_blocks(n_vertices), dim3(DEC_THREADS), 0, st, n_vertices, vmap);
-        if (int rc = launched("dgs_decimate_apply (init)")) return rc;
-    }
-    if (n_sel > 0 && n_edges > 0 && n_vertices > 0) {
-        hipLaunchKernelGGL(dec_collapse_kernel, dec_blocks(n_sel), dim3(DEC_THREADS), 0, st, n_vertices, pos, rows, colors, flags, moved, vmap, n_edges,
-                           edges, place, n_sel, sel);
-        if (int rc = launched("dgs_decimate_apply (collapse)")) return rc;
-    }
-    if (n_faces > 0) {
-        hipLaunchKernelGGL(dec_reindex_kernel, dec_blocks(n_faces), dim3(DEC_THREADS), 0, st, n_faces, faces, n_vertices, vmap, keep);
-        if (int rc = launched("dgs_decimate_apply (faces)")) return rc;
-    }
-    return 0;
+    const dim3 threads(DEC_THREADS);
+    if (int rc = launch_if(n_vertices > 0, w, "init", dec_iota_kernel, blocks_of_256(n_vertices), threads, stream, n_vertices, vmap)) return rc;
+    if (int rc = launch_if(n_sel > 0 && n_edges > 0 && n_vertices > 0, w, "collapse", dec_collapse_kernel, blocks_of_256(n_sel), threads, stream,
+                           n_vertices, pos, rows, colors, flags, moved, vmap, n_edges, edges, place, n_sel, sel))
+        return rc;
+    return launch_if(n_faces > 0, w, "faces", dec_reindex_kernel, blocks_of_256(n_faces), threads, stream, n_faces, faces, n_vertices, vmap,
+                     keep);
 }
 
 int dgs_decimate_layout(int out[8]) {
@@ -528,71 +520,63 @@ int dgs_decimate_layout(int out[8]) {
                                                DEC_LEN_BITS});
 }
 
+// ---- hole filling (mesh_fill_kernels.h) ------------------------------------------------------------------------------------------
 int dgs_fill_rank(long long n_nodes, const int* succ, const int* leader, int n_rounds, unsigned long long* buf_a, unsigned long long* buf_b,
                   int* rank, void* stream) {
-    if (int rc = dec_counts("dgs_fill_rank", {n_nodes})) return rc;
+    const char* w = "dgs_fill_rank";
+    if (int rc = check_counts(w, {n_nodes})) return rc;
     if (n_rounds < 0 || n_rounds > FILL_MAX_ROUNDS)
         return fail(-1, "dgs_fill_rank: n_rounds must be in [0, " + std::to_string(FILL_MAX_ROUNDS) + "] (2^n_rounds nodes are the longest list)");
     if (n_nodes > 0 && (!succ || !leader || !buf_a || !buf_b || !rank)) return fail(-1, "dgs_fill_rank: null pointer");
     if (n_nodes > 0 && buf_a == buf_b) return fail(-1, "dgs_fill_rank: buf_a and buf_b must be two buffers (a round reads one and writes the other)");
     if (n_nodes == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid = dec_blocks(n_nodes);
-    hipLaunchKernelGGL(fill_rank_init_kernel, grid, dim3(FILL_THREADS), 0, st, n_nodes, succ, leader, buf_a);
-    if (int rc = launched("dgs_fill_rank (init)")) return rc;
+    const dim3 grid = blocks_of_256(n_nodes), threads(FILL_THREADS);
+    if (int rc = launch(w, "init", fill_rank_init_kernel, grid, threads, stream, n_nodes, succ, leader, buf_a)) return rc;
     unsigned long long *in = buf_a, *out = buf_b;
     for (int r = 0; r < n_rounds; ++r) {
-        hipLaunchKernelGGL(fill_rank_round_kernel, grid, dim3(FILL_THREADS), 0, st, n_nodes, in, out);
-        if (int rc = launched("dgs_fill_rank (round)")) return rc;
+        if (int rc = launch(w, "round", fill_rank_round_kernel, grid, threads, stream, n_nodes, in, out)) return rc;
         std::swap(in, out);
     }
-    hipLaunchKernelGGL(fill_rank_final_kernel, grid, dim3(FILL_THREADS), 0, st, n_nodes, leader, in, rank);
-    return launched("dgs_fill_rank (ranks)");
+    return launch(w, "ranks", fill_rank_final_kernel, grid, threads, stream, n_nodes, leader, in, rank);
 }
 
 int dgs_fill_rim(long long n_vertices, const float* vertices, const float* colors, long long n_rim, const int* loop_vertices, const int* rim_loop,
                  long long n_loops, const long long* loop_offsets, double centre_x, double centre_y, double centre_z, double scale, double* S,
                  double* SC, long long* rows, void* stream) {
-    if (int rc = dec_counts("dgs_fill_rim", {n_vertices, n_rim, n_loops})) return rc;
+    const char* w = "dgs_fill_rim";
+    if (int rc = check_counts(w, {n_vertices, n_rim, n_loops})) return rc;
     FillFrame fr;
-    if (int rc = fill_frame("dgs_fill_rim", centre_x, centre_y, centre_z, scale, fr)) return rc;
+    if (int rc = fill_frame(w, centre_x, centre_y, centre_z, scale, fr)) return rc;
     if ((n_vertices > 0 && !vertices) || (n_rim > 0 && (!loop_vertices || !rim_loop || !S)) || (n_loops > 0 && (!loop_offsets || !rows)) ||
         (n_rim > 0 && (colors != nullptr) != (SC != nullptr)))
         return fail(-1, "dgs_fill_rim: null pointer (colors and SC come together)");
     if (n_loops == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(rows, 0, (size_t)n_loops * SIMP_ROW * sizeof(long long), st);
+    hipError_t e = hipMemsetAsync(rows, 0, (size_t)n_loops * SUM_ROW * sizeof(long long), (hipStream_t)stream);
     if (e != hipSuccess) return fail(-2, std::string("dgs_fill_rim (clear): ") + hipGetErrorString(e));
     if (n_rim == 0) return 0;
-    hipLaunchKernelGGL(fill_rim_kernel, dec_blocks(n_rim), dim3(FILL_THREADS), 0, st, n_vertices, vertices, colors, n_rim, loop_vertices, rim_loop,
-                       n_loops, loop_offsets, fr, S, SC, rows);
-    return launched("dgs_fill_rim");
+    return launch(w, nullptr, fill_rim_kernel, blocks_of_256(n_rim), dim3(FILL_THREADS), stream, n_vertices, vertices, colors, n_rim, loop_vertices, rim_loop,
+                  n_loops, loop_offsets, fr, S, SC, rows);
 }
 
 int dgs_fill_emit(long long n_old, long long n_new, const int* vert_ring, long long n_new_faces, const int* face_ring, long long n_rings,
                   const int* rings, long long n_loops, const long long* loop_offsets, long long n_rim, const int* loop_vertices,
                   const long long* rows, const double* S, const double* SC, double centre_x, double centre_y, double centre_z, double scale,
                   float* vertices_out, float* colors_out, int* faces_out, void* stream) {
-    if (int rc = dec_counts("dgs_fill_emit", {n_old, n_new, n_old + n_new, n_new_faces, n_rings, n_loops, n_rim})) return rc;
+    const char* w = "dgs_fill_emit";
+    if (int rc = check_counts(w, {n_old, n_new, n_old + n_new, n_new_faces, n_rings, n_loops, n_rim})) return rc;
     FillFrame fr;
-    if (int rc = fill_frame("dgs_fill_emit", centre_x, centre_y, centre_z, scale, fr)) return rc;
+    if (int rc = fill_frame(w, centre_x, centre_y, centre_z, scale, fr)) return rc;
     const bool any = n_new > 0 || n_new_faces > 0;
     if ((n_new > 0 && !vert_ring) || (n_new_faces > 0 && (!face_ring || !faces_out)) || (n_old + n_new > 0 && any && !vertices_out) ||
         (any && (!rings || !loop_offsets || !loop_vertices || !rows || !S)) || (n_new > 0 && (colors_out != nullptr) != (SC != nullptr)))
         return fail(-1, "dgs_fill_emit: null pointer (colors_out and SC come together)");
     if (any && (n_rings == 0 || n_loops == 0 || n_rim == 0)) return fail(-1, "dgs_fill_emit: new vertices or faces without rings, loops or a rim");
-    hipStream_t st = (hipStream_t)stream;
-    if (n_new > 0) {
-        hipLaunchKernelGGL(fill_vertex_kernel, dec_blocks(n_new), dim3(FILL_THREADS), 0, st, n_old, n_new, vert_ring, n_rings, rings, n_loops,
-                           loop_offsets, n_rim, rows, S, SC, fr, vertices_out, colors_out);
-        if (int rc = launched("dgs_fill_emit (vertices)")) return rc;
-    }
-    if (n_new_faces > 0) {
-        hipLaunchKernelGGL(fill_face_kernel, dec_blocks(n_new_faces), dim3(FILL_THREADS), 0, st, n_old + n_new, n_new_faces, face_ring, n_rings, rings,
-                           n_loops, loop_offsets, n_rim, loop_vertices, rows, vertices_out, faces_out);
-        if (int rc = launched("dgs_fill_emit (faces)")) return rc;
-    }
-    return 0;
+    if (int rc = launch_if(n_new > 0, w, "vertices", fill_vertex_kernel, blocks_of_256(n_new), dim3(FILL_THREADS), stream, n_old, n_new, vert_ring,
+                           n_rings, rings, n_loops, loop_offsets, n_rim, rows, S, SC, fr, vertices_out, colors_out))
+        return rc;
+    return launch_if(n_new_faces > 0, w, "faces", fill_face_kernel, blocks_of_256(n_new_faces), dim3(FILL_THREADS), stream, n_old + n_new,
+                     n_new_faces, face_ring, n_rings, rings, n_loops, loop_offsets, n_rim, loop_vertices, rows, vertices_out,
+                     faces_out);
 }
 
 int dgs_fill_layout(int out[8]) {

@@ -20,6 +20,8 @@ connects nothing."""
 import numpy as np
 import torch
 
+from .mesh_topology import _check_mesh, _compact, _first_proper_faces, half_edges, sorted_edge_keys
+
 _ADJACENCY = ("vertex", "edge")
 
 
@@ -79,17 +81,6 @@ def component_labels(groups, n_nodes):
 
 
 # ---- triangles ------------------------------------------------------------------------------------------------------------------
-def _check_mesh(what, vertices, faces, colors=None):
-    if not torch.is_tensor(vertices) or vertices.dim() != 2 or vertices.shape[1] != 3 or not vertices.is_floating_point():
-        raise ValueError("%s: vertices must be a floating-point tensor [V,3]" % what)
-    if not torch.is_tensor(faces) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int32, torch.int64):
-        raise ValueError("%s: faces must be an int32 or int64 tensor [F,3]" % what)
-    if faces.device != vertices.device or (colors is not None and (colors.device != vertices.device or colors.shape[0] != vertices.shape[0])):
-        raise ValueError("%s: vertices, faces and colors must live on one device, one colour per vertex" % what)
-    if vertices.shape[0] >= 2 ** 31 or faces.shape[0] >= 2 ** 31:
-        raise ValueError("%s: at most 2^31 - 1 vertices and faces" % what)
-
-
 def _face_labels(n_vertices, faces, adjacency):
     """[F] int64: a label per face that is equal for two faces iff they are in one cluster (a vertex id under "vertex", a face id
     under "edge").  Raises ValueError for a vertex id outside [0, n_vertices)."""
@@ -102,11 +93,10 @@ def _face_labels(n_vertices, faces, adjacency):
     lo, hi = (int(x) for x in torch.stack(torch.aminmax(f)).tolist())
     if lo < 0 or hi >= n_vertices:
         raise ValueError("component_labels: node ids in [%d, %d] but n_nodes is %d" % (lo, hi, n_vertices))
-    a, b = f, f.roll(-1, 1)                                   # edge e of face i: corners e and e + 1; flat index 3 i + e
-    key = (torch.minimum(a, b) * n_vertices + torch.maximum(a, b)).reshape(-1)      # < 2^62
-    key, order = torch.sort(torch.where((a != b).reshape(-1), key, torch.full_like(key, -1)))
+    key, order = sorted_edge_keys(*half_edges(f))            # edge e of face i: corners e and e + 1; half-edge 3 i + e
     face = order // 3
-    pair = (key[1:] == key[:-1]) & (key[1:] >= 0)             # neighbours in a run of equal keys: a run of m faces gives a chain of m - 1 pairs
+    # neighbours in a run of equal keys: a run of m faces gives a chain of m - 1 pairs; a key of two equal halves is no edge
+    pair = (key[1:] == key[:-1]) & ((key[1:] >> 32) != (key[1:] & 0xFFFFFFFF))
     groups = torch.stack((face[:-1][pair], face[1:][pair]), -1)
     return component_labels(groups, F)
 
@@ -159,33 +149,6 @@ def cluster_connected_triangles(vertices, faces, adjacency="vertex"):
     counts = _label_counts(cluster, n)[0]
     area = torch.zeros(n, dtype=torch.float64, device=faces.device).index_add_(0, cluster, face_areas(vertices, faces))
     return cluster, counts, area
-
-
-def _compact(vertices, faces, colors, keep_face):
-    """Keep the faces of the mask, drop the vertices nothing refers to, renumber: the tail of mesh.keep_largest_components."""
-    f = faces[keep_face]
-    used = torch.zeros(vertices.shape[0], dtype=torch.bool, device=vertices.device)
-    used[f.reshape(-1).long()] = True
-    remap = torch.cumsum(used, 0) - 1
-    f = remap[f.long()].to(faces.dtype)
-    return vertices[used], f, None if colors is None else colors[used]
-
-
-def _first_proper_faces(f):
-    """[F] bool for faces f [F,3] int64: steps (b) and (c) of clean_mesh (simplify_mesh applies them to the cluster ids) -- true for
-    a face that names three different vertices and repeats no earlier face up to a rotation of its corners."""
-    F, dev = f.shape[0], f.device
-    keep = torch.ones(F, dtype=torch.bool, device=dev)
-    if F:
-        # (b): rotate the smallest corner to the front; rows that are equal then are rotations of each other
-        shift = f.argmin(1, keepdim=True)
-        canon = torch.gather(f, 1, (shift + torch.arange(3, device=dev)) % 3)
-        _, inverse = torch.unique(canon, dim=0, return_inverse=True)
-        ids = torch.arange(F, dtype=torch.int64, device=dev)
-        first = torch.full((F,), F, dtype=torch.int64, device=dev).scatter_reduce_(0, inverse, ids, "amin")
-        keep = first[inverse] == ids
-        keep &= (f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 2] != f[:, 0])          # (c)
-    return keep
 
 
 @torch.no_grad()

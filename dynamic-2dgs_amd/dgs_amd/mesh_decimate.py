@@ -22,9 +22,10 @@ import math
 import numpy as np
 import torch
 
-from .mesh_clean import _check_mesh, _compact
+from .mesh_topology import (LAMBDA_EXP, _check_mesh, _compact, _cross, _dot, _frame, _kernels, _three_distinct, half_edges, normal_lengths, quadric_solve,
+                            sorted_edge_keys)
 
-W_MAX, LAMBDA_EXP = 16, -10            # largest face weight (in mean face areas), lambda = 2^LAMBDA_EXP
+W_MAX = 16                             # largest face weight (in mean face areas); lambda = 2^LAMBDA_EXP
 Q_MAX, Q_BUDGET = 40, 59               # fixed-point bits of the quadric sums: Q = min(Q_MAX, Q_BUDGET - ceil(log2(F)))
 LEN_BITS = 28                          # fixed-point bits of the face-normal lengths behind the mean face area
 MIN_VALENCE = 5                        # an interior vertex opposite a collapsed edge must have at least this many neighbours
@@ -62,8 +63,8 @@ def round_tables(n_vertices, f, preserve_boundary=True):
       vf_offsets [V+1] int64, vf [3F] int32            the faces of every vertex, rows ascending
     and "dkey" [2E] int64, the sorted directed pairs i << 32 | j behind adj (the statement's membership test)."""
     V, F, dev = int(n_vertices), f.shape[0], f.device
-    i, j, opp = f.reshape(-1), f.roll(-1, 1).reshape(-1), f.roll(-2, 1).reshape(-1)     # half-edge 3 g + c: corners c, c + 1; opposite c + 2
-    key, order = torch.sort((torch.minimum(i, j) << 32) | torch.maximum(i, j), stable=True)   # equal keys stay in face order
+    (i, j), opp = half_edges(f), f.roll(-2, 1).reshape(-1)  # half-edge 3 g + c: corners c, c + 1; opposite c + 2
+    key, order = sorted_edge_keys(i, j)                      # equal keys stay in face order
     ekey, count = torch.unique_consecutive(key, return_counts=True)
     start = torch.cumsum(count, 0) - count
     opp_s = opp[order]
@@ -92,21 +93,6 @@ def round_tables(n_vertices, f, preserve_boundary=True):
 
 
 # ---- the statement --------------------------------------------------------------------------------------------------------------
-def _cross(a, b):
-    return torch.stack((a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2], a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]), -1)
-
-
-def _dot(a, b):
-    return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
-
-
-def normal_lengths(pos, f):
-    """l [F] fp32 of step 1: the fp32 normal (b - a) x (c - a) and its length through the fp64 square root."""
-    p = pos[f]
-    n = _cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
-    return n, torch.sqrt(_dot(n, n).double()).float()
-
-
 def mean_length(l):
     """The mean of the countable lengths as an fp32 Python number, from an integer sum (exact on every device): every term is
     rounded UP to a multiple of 2^-LEN_BITS, so the mean is not below the true one and the weights sum to at most F."""
@@ -139,21 +125,6 @@ def quadrics_torch(pos, f, mean_len, q_bits):
     return rows
 
 
-def _solve(r, mid):
-    """(y [E,3] fp64, good [E]): the regularised system of step 2b for summed rows r [E,10] fp64 and midpoints mid [E,3] fp64."""
-    a00, a01, a02, a11, a12, a22, b0, b1, b2 = (r[:, k] for k in range(9))
-    t = (a00 + a11) + a22
-    g = t * 2.0 ** LAMBDA_EXP
-    m00, m11, m22 = a00 + g, a11 + g, a22 + g
-    r0, r1, r2 = g * mid[:, 0] - b0, g * mid[:, 1] - b1, g * mid[:, 2] - b2
-    c00, c01, c02 = m11 * m22 - a12 * a12, a02 * a12 - a01 * m22, a01 * a12 - a02 * m11
-    c11, c12, c22 = m00 * m22 - a02 * a02, a01 * a02 - m00 * a12, m00 * m11 - a01 * a01
-    det = (m00 * c00 + a01 * c01) + a02 * c02
-    y = torch.stack((((c00 * r0 + c01 * r1) + c02 * r2) / det, ((c01 * r0 + c11 * r1) + c12 * r2) / det,
-                     ((c02 * r0 + c12 * r1) + c22 * r2) / det), -1)
-    return y, (t > 0) & (det > 0) & torch.isfinite(det)
-
-
 def _expand(offsets, ids, rows_of):
     """All (item, entry) pairs of the CSR rows rows_of [N]: (item index [M], entry [M])."""
     b, n = offsets[rows_of], offsets[rows_of + 1] - offsets[rows_of]
@@ -174,7 +145,7 @@ def edge_costs_torch(pos, rows, f, tab, q_bits, max_cost):
     pu, pv = pos[u].double(), pos[v].double()
     mid = (pu + pv) * 0.5
     r = (rows[u] + rows[v]).double()
-    y, good = _solve(r, mid)
+    y, good = quadric_solve([r[:, k] for k in range(6)], [r[:, 6 + k] for k in range(3)], mid)
     dlt = pv - pu
     rad = (dlt[:, 0].abs() + dlt[:, 1].abs()) + dlt[:, 2].abs()
     good = good & ((y - mid).abs() <= rad[:, None]).all(1)
@@ -285,16 +256,6 @@ class _State:
     faces [F,3] int64 (ids of the input), rep [V] int64 (the vertex every input vertex has been merged into)."""
 
 
-_STATEMENT_EVERYWHERE = False          # tools/mesh_decimate_timing.py sets it to time the PyTorch statement on a HIP device; nothing else does
-
-
-def _kernels(dev):
-    if dev.type == "cpu" or _STATEMENT_EVERYWHERE:
-        return None
-    from . import _mesh_ops   # a missing library is an error, never a reason to run the PyTorch statement instead
-    return _mesh_ops
-
-
 def decimate_round(st, target, q_bits, max_cost, preserve_boundary, oversubscribe=None, clock=None):
     """One round on the state -> (collapses applied, dict of the round's tensors for the tests and the timing tool).  clock: called
     with the name of every phase as it ends (the timing tool's stopwatch)."""
@@ -348,21 +309,12 @@ def decimate_round(st, target, q_bits, max_cost, preserve_boundary, oversubscrib
     return n_sel, out
 
 
-def _frame(vertices):
-    """(centre [3] fp32 tensor, scale: a power of two) -- |(v - centre) * scale| <= 1 (+ one rounding) per axis."""
-    lo, hi = vertices.amin(0), vertices.amax(0)
-    centre = (lo + hi) * 0.5
-    half = float(((hi - lo) * 0.5).max())
-    exp = 0 if not (half > 0.0 and math.isfinite(half)) else min(max(math.frexp(half)[1], -100), 100)
-    return centre, 2.0 ** -exp
-
-
 def prepare(vertices, faces, colors, preserve_boundary=True):
     """Step 0 and step 1 -> (state, q_bits, scale, centre); the faces that name a vertex twice are dropped here."""
     dev = vertices.device
     V = vertices.shape[0]
     f = faces.long()
-    f = f[(f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 2] != f[:, 0])]
+    f = f[_three_distinct(f)]
     centre, scale = _frame(vertices)
     st = _State()
     st.pos = ((vertices - centre) * scale).contiguous()

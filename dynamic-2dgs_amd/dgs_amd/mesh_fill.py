@@ -24,24 +24,14 @@ non-planar."""
 import numpy as np
 import torch
 
-from .mesh_clean import _check_mesh, component_labels
-from .mesh_decimate import _cross, _dot, _frame
-from .mesh_smooth import _faces_checked
+from .mesh_clean import component_labels
+from .mesh_topology import _check_mesh, _cross, _dot, _faces_checked, _frame, _kernels, _three_distinct, half_edges, sorted_edge_keys
 
 POS_BITS, NRM_BITS, COL_BITS = 30, 28, 24              # fixed-point bits of the position, Newell and colour sums of a loop
 TAPS = (1.0 / 256, 8.0 / 256, 28.0 / 256, 56.0 / 256, 70.0 / 256, 56.0 / 256, 28.0 / 256, 8.0 / 256, 1.0 / 256)   # [1/4 1/2 1/4] four times
 RING_COLS = 10                                         # loop, k, R, n, count, first vertex, count before, first vertex before, first face, faces
 DEFAULT_MAX_HOLE_EDGES = 128                           # a policy, not a measurement: a hole about 20 voxels across
 _ID_LIMIT = 2 ** 31                                    # vertex and face totals stay below it (ids are int32 in the kernels)
-
-_STATEMENT_EVERYWHERE = False          # tools/mesh_fill_timing.py sets it to time the PyTorch statement on a HIP device; nothing else does
-
-
-def _kernels(dev):
-    if dev.type == "cpu" or _STATEMENT_EVERYWHERE:
-        return None
-    from . import _mesh_ops   # a missing library is an error, never a reason to run the PyTorch statement instead
-    return _mesh_ops
 
 
 def ring_count(n):
@@ -63,21 +53,21 @@ def fill_counts(n):
 
 # ---- half-edges and loops (PyTorch on the tensors' device, integers only) -------------------------------------------------------
 def _proper(f):
-    return f[(f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 2] != f[:, 0])]
+    return f[_three_distinct(f)]
 
 
 def boundary_half_edges(n_vertices, f):
     """The nodes of step 1 for faces f [F,3] int64 (three different vertices each) -> (tail [NB], head [NB], face [NB]) int64, in
     ascending order of (tail, head): the half-edges (a -> b) whose undirected edge occurs once among all half-edges, and the face
     each comes from.  One sort of the 3 F packed keys min << 32 | max, and one of the NB boundary half-edges."""
-    a, b = f.reshape(-1), f.roll(-1, 1).reshape(-1)           # half-edge 3 g + c: corners c, c + 1 of face g
+    a, b = half_edges(f)
     if a.shape[0] == 0:
         z = torch.zeros(0, dtype=torch.int64, device=f.device)
         return z, z, z
-    key, order = torch.sort((torch.minimum(a, b) << 32) | torch.maximum(a, b))
+    key, order = sorted_edge_keys(a, b)
     differs = key[1:] != key[:-1]
     edge = torch.ones(1, dtype=torch.bool, device=f.device)
-    once = order[torch.cat((edge, differs)) & torch.cat((differs, edge))]
+    once = order[torch.cat((edge, differs)) & torch.cat((differs, edge))]                     # a run of one: both neighbours differ
     tail, head = a[once], b[once]
     by_tail = torch.sort((tail << 32) | head).indices
     return tail[by_tail], head[by_tail], (once // 3)[by_tail]
@@ -182,9 +172,9 @@ def is_watertight(n_vertices, faces):
     f = _proper(_faces_checked("is_watertight", n_vertices, faces))
     if f.shape[0] == 0:
         return False
-    a, b = f.reshape(-1), f.roll(-1, 1).reshape(-1)
+    a, b = half_edges(f)
     directed = torch.sort((a << 32) | b).values
-    count = torch.unique_consecutive(torch.sort((torch.minimum(a, b) << 32) | torch.maximum(a, b)).values, return_counts=True)[1]
+    count = torch.unique_consecutive(sorted_edge_keys(a, b)[0], return_counts=True)[1]
     return bool((count == 2).all() & (directed[1:] != directed[:-1]).all())
 
 

@@ -16,9 +16,9 @@ import math
 import numpy as np
 import torch
 
-from .mesh_clean import _check_mesh, _compact, _first_proper_faces
+from .mesh_topology import LAMBDA_EXP, _check_mesh, _compact, _first_proper_faces, face_normals, quadric_solve
 
-Q, W_MAX, LAMBDA_EXP = 24, 16, -10        # fixed-point bits of the quadric sums, largest face weight, lambda = 2^LAMBDA_EXP
+Q, W_MAX = 24, 16                         # fixed-point bits of the quadric sums, largest face weight (lambda = 2^LAMBDA_EXP)
 POS_BITS, COL_BITS = 30, 24               # fixed-point bits of the position and colour sums
 GRID_BITS = 21                            # cells per axis: ijk in [0, 2^21)
 _PLACEMENT = ("average", "quadric")
@@ -58,10 +58,7 @@ def _accumulate_torch(vertices, colors, faces, cluster, centre, cell):
     if faces.shape[0]:
         p = vertices[faces]                                                     # [F,3 corners,3]
         k = cluster[faces]                                                      # [F,3]
-        e1, e2 = p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]
-        n = torch.stack((e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
-                         e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]), -1)
-        l = torch.sqrt(((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2]).double()).float()     # fp64: the device's fp32 sqrt is not correctly rounded
+        n, l = face_normals(p)
         ok = (l > 0) & torch.isfinite(l)
         p, k, n, l = p[ok], k[ok], n[ok], l[ok]
         nh = n / l[:, None]
@@ -86,17 +83,8 @@ def _solve_torch(rows, centre, cell, quadric, with_colors):
     xb = torch.nan_to_num(r[:, 1:4] / (count * float(2 ** POS_BITS))[:, None], nan=0.0).clamp(-1.0, 1.0)
     x = xb
     if quadric:
-        a00, a01, a02, a11, a12, a22, b0, b1, b2 = (r[:, 7 + i] for i in range(9))
-        t = (a00 + a11) + a22
-        g = t * 2.0 ** LAMBDA_EXP
-        m00, m11, m22 = a00 + g, a11 + g, a22 + g
-        r0, r1, r2 = g * xb[:, 0] - b0, g * xb[:, 1] - b1, g * xb[:, 2] - b2
-        c00, c01, c02 = m11 * m22 - a12 * a12, a02 * a12 - a01 * m22, a01 * a12 - a02 * m11
-        c11, c12, c22 = m00 * m22 - a02 * a02, a01 * a02 - m00 * a12, m00 * m11 - a01 * a01
-        det = (m00 * c00 + a01 * c01) + a02 * c02
-        y = torch.stack((((c00 * r0 + c01 * r1) + c02 * r2) / det, ((c01 * r0 + c11 * r1) + c12 * r2) / det,
-                         ((c02 * r0 + c12 * r1) + c22 * r2) / det), -1)
-        good = (t > 0) & (det > 0) & torch.isfinite(det) & (y.abs() <= 1.0).all(1)
+        y, good = quadric_solve([r[:, 7 + i] for i in range(6)], [r[:, 13 + i] for i in range(3)], xb)
+        good = good & (y.abs() <= 1.0).all(1)
         x = torch.where(good[:, None], y, xb)
     vertices = centre + x.float() * cell
     colors = None

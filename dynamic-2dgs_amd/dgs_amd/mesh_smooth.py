@@ -21,28 +21,13 @@ import math
 import numpy as np
 import torch
 
-from .mesh_clean import _check_mesh
+from .mesh_topology import _check_mesh, _faces_checked, undirected_edges
 
 _METHODS = ("simple", "laplacian", "taubin")
 MODE_LAPLACIAN, MODE_SIMPLE = 0, 1
 
 
 # ---- adjacency ------------------------------------------------------------------------------------------------------------------
-def _faces_checked(what, n_vertices, faces):
-    """faces [F,3] as int64 after the range check (one aminmax, read on the host)."""
-    if not torch.is_tensor(faces) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int32, torch.int64):
-        raise ValueError("%s: faces must be an int32 or int64 tensor [F,3]" % what)
-    n_vertices = int(n_vertices)
-    if n_vertices < 0 or n_vertices >= 2 ** 31:
-        raise ValueError("%s: n_vertices must be in [0, 2^31)" % what)
-    f = faces.long()
-    if f.shape[0]:
-        lo, hi = (int(x) for x in torch.stack(torch.aminmax(f)).tolist())
-        if lo < 0 or hi >= n_vertices:
-            raise ValueError("%s: face index out of range (ids in [%d, %d], %d vertices)" % (what, lo, hi, n_vertices))
-    return f
-
-
 def vertex_adjacency(n_vertices, faces):
     """(offsets [V+1] int64, neighbours [E] int32) on the device of faces [F,3]: row i = neighbours[offsets[i]:offsets[i+1]] lists
     the distinct vertices j != i that share a face with i, ascending.  From the six directed pairs of every face, packed as
@@ -65,17 +50,14 @@ def vertex_adjacency(n_vertices, faces):
 
 
 def boundary_vertices(n_vertices, faces):
-    """bool [V] on the device of faces: the endpoints of the undirected edges that lie in exactly one face (edges counted with
-    unique(return_counts=True); an edge from a vertex to itself is no edge).  ValueError: a face index outside [0, V)."""
+    """bool [V] on the device of faces: the endpoints of the undirected edges that lie in exactly one face (the runs of
+    mesh_topology.undirected_edges of length 1; an edge from a vertex to itself is no edge).  ValueError: a face index outside [0, V)."""
     f = _faces_checked("boundary_vertices", n_vertices, faces)
     V, dev = int(n_vertices), faces.device
     mark = torch.zeros(V, dtype=torch.bool, device=dev)
-    i = torch.cat((f[:, 0], f[:, 1], f[:, 2]))
-    j = torch.cat((f[:, 1], f[:, 2], f[:, 0]))
-    keep = i != j
-    lo, hi = torch.minimum(i, j)[keep], torch.maximum(i, j)[keep]
-    key, count = torch.unique((lo << 32) | hi, return_counts=True)
-    once = key[count == 1]
+    key, _, start, count = undirected_edges(f)
+    edge = key[start]
+    once = edge[(count == 1) & ((edge >> 32) != (edge & 0xFFFFFFFF))]
     mark[once >> 32] = True
     mark[once & 0xFFFFFFFF] = True
     return mark

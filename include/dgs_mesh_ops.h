@@ -337,7 +337,7 @@ int dgs_cc_layout(int out[2]);
  * int32, centres [n_clusters,3], rows [n_clusters,16] int64 (cleared by the call).  Up to three operations on `stream`: the clear,
  * a launch over the vertices, a launch over the faces.  A workgroup keeps its items' keys and values in LDS, finds the runs of
  * neighbouring items with one cluster, and sums every run on chip; a run then costs one 64-bit atomic per non-zero column, 16 lanes
- * on the 128 contiguous bytes of one row (csrc/mesh_cc_kernels.h).  A vertex id outside [0, n_vertices) drops its face, a cluster
+ * on the 128 contiguous bytes of one row (csrc/mesh_common.h).  A vertex id outside [0, n_vertices) drops its face, a cluster
  * id outside [0, n_clusters) drops that vertex or that corner's contribution: index guards, so no address leaves a buffer; the
  * Python wrapper produces no such ids.
  * Refused with a negative status before any launch: a negative count, a count >= 2^31, cell not positive and finite, a null pointer

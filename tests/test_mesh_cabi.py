@@ -43,7 +43,8 @@ def test_mesh_library_is_separate_from_the_training_libraries():
     from diff_surfel_rasterization import _C
     mine = {os.path.basename(p) for p in _mesh_ops._deps()}
     assert mine == {"mesh_ops.hip", "mesh_common.h", "mesh_fusion_kernels.h", "mesh_search_kernels.h", "mesh_raster_kernels.h",
-                    "mesh_cc_kernels.h", HEADER}
+                    "mesh_cc_kernels.h", "mesh_simplify_kernels.h", "mesh_smooth_kernels.h", "mesh_decimate_kernels.h",
+                    "mesh_fill_kernels.h", HEADER}
     assert not mine & {os.path.basename(p) for p in _ops._deps() + _C._deps()}
     assert "-ffp-contract=off" in _mesh_ops.HIPCC_FLAGS and set(_ops.HIPCC_FLAGS) <= set(_mesh_ops.HIPCC_FLAGS)
 

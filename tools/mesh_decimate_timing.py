@@ -105,7 +105,7 @@ def main():
     ap.add_argument("--no-statement", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_decimate_timing.json"))
     a = ap.parse_args()
-    from dgs_amd import mesh_decimate as md
+    from dgs_amd import mesh_decimate as md, mesh_topology
     dev = torch.device(a.device)
     result = {"device": torch.cuda.get_device_name(0) if dev.type != "cpu" else "cpu", "oversubscribe": md.OVERSUBSCRIBE, "meshes": []}
     if dev.type != "cpu":
@@ -149,11 +149,11 @@ def main():
         if dev.type != "cpu" and not a.no_statement:
             ratio = a.ratios[0]
             want = md.decimate_mesh(v, f, c, ratio=ratio, return_map=True)
-            md._STATEMENT_EVERYWHERE = True
+            mesh_topology._STATEMENT_EVERYWHERE = True
             try:
                 ms, got = wall(lambda: md.decimate_mesh(v, f, c, ratio=ratio, return_map=True))
             finally:
-                md._STATEMENT_EVERYWHERE = False
+                mesh_topology._STATEMENT_EVERYWHERE = False
             same = all((x is None and y is None) or (x.shape == y.shape and torch.equal(x.view(torch.int32) if x.is_floating_point() else x,
                                                                                          y.view(torch.int32) if y.is_floating_point() else y))
                        for x, y in zip(want, got))

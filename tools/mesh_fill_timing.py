@@ -31,7 +31,7 @@ from mesh_timing import cameras, stats, timed, truth_model
 
 def punch(v, f, c, n_holes, seed=0):
     """Take n_holes discs of faces out of the mesh, on its device: the faces whose corners all lie within r rings of a seed."""
-    from dgs_amd.mesh_clean import _compact
+    from dgs_amd.mesh_topology import _compact
     V, fl = v.shape[0], f.long()
     g = torch.Generator().manual_seed(seed)
     seeds = torch.randint(0, V, (n_holes,), generator=g).tolist()
@@ -60,9 +60,9 @@ def main():
     ap.add_argument("--max-edges", type=int, default=128)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_fill_timing.json"))
     a = ap.parse_args()
-    from dgs_amd import _mesh_ops, mesh_fill as mf
+    from dgs_amd import _mesh_ops, mesh_fill as mf, mesh_topology
     from dgs_amd.mesh import TSDFVolume, views_at_time
-    from dgs_amd.mesh_decimate import _frame
+    from dgs_amd.mesh_topology import _frame
     dev = torch.device("cuda:0")
     t = 0.25
     model = truth_model(t, dev)
@@ -80,11 +80,11 @@ def main():
         fill = lambda: mf.fill_holes(v, f, c, max_hole_edges=a.max_edges)
 
         def statement():
-            mf._STATEMENT_EVERYWHERE = True
+            mesh_topology._STATEMENT_EVERYWHERE = True
             try:
                 return mf.fill_holes(v, f, c, max_hole_edges=a.max_edges)
             finally:
-                mf._STATEMENT_EVERYWHERE = False
+                mesh_topology._STATEMENT_EVERYWHERE = False
 
         want, got = fill(), statement()                      # warm-up of both (the library, the allocator)
         torch.cuda.synchronize()
