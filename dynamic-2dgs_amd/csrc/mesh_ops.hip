@@ -1,5 +1,5 @@
 // libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion of rendered depth maps, marching tetrahedra, the all-pairs
-// nearest-neighbour and closest-triangle searches and the earth mover's distance (an auction solver) of the mesh metrics, the
+// nearest-neighbour and closest-triangle searches, the winding-number sums and the earth mover's distance (an auction solver) of the mesh metrics, the
 // z-buffer triangle rasterizer of the mesh images, the connected components of the mesh clean-up, the quadric vertex
 // clustering of the mesh simplification, the Laplacian / Taubin steps of the mesh smoothing, the quadric edge collapse of the
 // mesh decimation and the list ranking and ring emission of the mesh hole filling, gfx950.
@@ -85,13 +85,18 @@ unsigned blocks_for(long long n, long long cap) {
     return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
 }
 
-// ---- the two searches -----------------------------------------------------------------------------------------------------------
-// dgs_nn_search and dgs_tri_search differ by these nouns and sizes and by the kernel they launch; search() is everything else.
+// ---- the all-pairs searches -----------------------------------------------------------------------------------------------------
+// dgs_nn_search, dgs_tri_search and dgs_winding_sum differ by these nouns and sizes and by the kernel they launch; search() is
+// everything else.
 struct Search {
-    const char *what, *empty, *count, *item, *chunk;   // entry point; refusal of an empty set; names of n_*, the low word, *_chunk
+    const char *what, *empty, *count, *why, *chunk;    // entry point; refusal of an empty set; name of n_*, why it stays below 2^31, name of *_chunk
     int per_block;                                     // queries of a workgroup
     size_t align;                                      // alignment of the set's pointer, bytes
+    int fill;                                          // the byte the output starts from: 0xFF under a minimum, 0 under a sum
 };
+const char* const kLowWordIndex = "the index is the low 32 bits of the packed minimum";
+const char* const kLowWordFace = "the face is the low 32 bits of the packed minimum";
+const char* const kWindingTerms = "the sum of n_tri terms below 2^30 stays below 2^61";
 
 template <class Launch>
 int search(const Search& s, long long n_query, const float* query, long long n_set, const float* set, long long chunk, unsigned long long* best,
@@ -99,7 +104,7 @@ int search(const Search& s, long long n_query, const float* query, long long n_s
     const std::string w = s.what;
     if (n_query < 0) return fail(-1, w + ": negative n_query");
     if (n_set < 1) return fail(-1, w + ": " + s.empty);
-    if (n_set >= (1LL << 31)) return fail(-1, w + ": " + s.count + " must be below 2^31 (the " + s.item + " is the low 32 bits of the packed minimum)");
+    if (n_set >= (1LL << 31)) return fail(-1, w + ": " + s.count + " must be below 2^31 (" + s.why + ")");
     if (chunk < 1) return fail(-1, w + ": " + s.chunk + " must be >= 1");
     if (!set || (n_query > 0 && (!query || !best))) return fail(-1, w + ": null pointer");
     if ((size_t)set % s.align != 0) return fail(-1, w + ": the table must be " + std::to_string(s.align) + "-byte aligned");
@@ -108,7 +113,7 @@ int search(const Search& s, long long n_query, const float* query, long long n_s
     const long long slices = (n_set + chunk - 1) / chunk, blocks = (n_query + s.per_block - 1) / s.per_block;
     if (slices > 65535) return fail(-1, w + ": more than 65535 slices: raise " + s.chunk);
     if (blocks > 0x7FFFFFFFLL) return fail(-1, w + ": too many queries for one launch");
-    hipError_t e = hipMemsetAsync(best, 0xFF, (size_t)n_query * sizeof(unsigned long long), (hipStream_t)stream);
+    hipError_t e = hipMemsetAsync(best, s.fill, (size_t)n_query * sizeof(unsigned long long), (hipStream_t)stream);
     if (e != hipSuccess) return fail(-2, w + " (init): " + hipGetErrorString(e));
     return launch_kernel(dim3((unsigned)blocks, (unsigned)slices), chunk);
 }
@@ -199,10 +204,10 @@ int dgs_mt_emit(int Nx, int Ny, int Nz, float ox, float oy, float oz, float voxe
                   point_mask, vert_incl, faces);
 }
 
-// ---- the two searches and the earth mover's distance (mesh_search_kernels.h) -----------------------------------------------------
+// ---- the searches, the winding sums and the earth mover's distance (mesh_search_kernels.h) -----------------------------------------------------
 int dgs_nn_search(long long n_query, const float* query, long long n_ref, const float* ref, long long ref_chunk, unsigned long long* best,
                   void* stream) {
-    const Search s{"dgs_nn_search", "the reference set must hold at least one point (n_ref >= 1)", "n_ref", "index", "ref_chunk", NN_Q, 1};
+    const Search s{"dgs_nn_search", "the reference set must hold at least one point (n_ref >= 1)", "n_ref", kLowWordIndex, "ref_chunk", NN_Q, 1, 0xFF};
     return search(s, n_query, query, n_ref, ref, ref_chunk, best, stream, [&](dim3 grid, long long chunk) {
         return launch(s.what, nullptr, nn_search_kernel, grid, dim3(NN_THREADS), stream, n_query, query, n_ref, ref, chunk, best);
     });
@@ -212,7 +217,7 @@ int dgs_nn_layout(int out[3]) { return layout("dgs_nn_layout", out, {NN_Q, NN_T,
 
 int dgs_tri_search(long long n_query, const float* query, long long n_tri, const float* table, long long tri_chunk, unsigned long long* best,
                    void* stream) {
-    const Search s{"dgs_tri_search", "the table must hold at least one triangle (n_tri >= 1)", "n_tri", "face", "tri_chunk", TRI_Q, 16};
+    const Search s{"dgs_tri_search", "the table must hold at least one triangle (n_tri >= 1)", "n_tri", kLowWordFace, "tri_chunk", TRI_Q, 16, 0xFF};
     return search(s, n_query, query, n_tri, table, tri_chunk, best, stream, [&](dim3 grid, long long chunk) {
         return launch(s.what, nullptr, tri_search_kernel, grid, dim3(TRI_THREADS), stream, n_query, query, n_tri,
                       reinterpret_cast<const float4*>(table), chunk, best);
@@ -220,6 +225,18 @@ int dgs_tri_search(long long n_query, const float* query, long long n_tri, const
 }
 
 int dgs_tri_layout(int out[4]) { return layout("dgs_tri_layout", out, {TRI_Q, TRI_T, TRI_CHUNK, TRI_ROW}); }
+
+int dgs_winding_sum(long long n_query, const float* query, long long n_tri, const float* table, long long tri_chunk, long long* sums,
+                    void* stream) {
+    const Search s{"dgs_winding_sum", "the table must hold at least one triangle (n_tri >= 1)", "n_tri", kWindingTerms, "tri_chunk", WIND_Q, 16, 0};
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(sums);
+    return search(s, n_query, query, n_tri, table, tri_chunk, out, stream, [&](dim3 grid, long long chunk) {
+        return launch(s.what, nullptr, winding_sum_kernel, grid, dim3(WIND_THREADS), stream, n_query, query, n_tri,
+                      reinterpret_cast<const float4*>(table), chunk, out);
+    });
+}
+
+int dgs_winding_layout(int out[4]) { return layout("dgs_winding_layout", out, {WIND_Q, WIND_T, WIND_CHUNK, WIND_ROW}); }
 
 int dgs_emd_auction(long long n, const float* a, const float* b, float inv_q, long long max_rounds, void* scratch, long long scratch_bytes,
                     int* assignment, long long* prices, long long* result, void* stream) {

@@ -1,6 +1,7 @@
-// mesh_search_kernels.h -- the all-pairs searches of the mesh metrics (mesh_ops.hip: dgs_nn_search, dgs_tri_search and, at the end,
-// the kernels of dgs_emd_auction).  The first two kernels share their shape and nothing else: each keeps its own statement of the
-// query state and the packed-minimum commit; the auction's bidding pass keeps a top-2 and is described with its kernels.
+// mesh_search_kernels.h -- the all-pairs searches of the mesh metrics (mesh_ops.hip: dgs_nn_search, dgs_tri_search, dgs_winding_sum
+// and, at the end, the kernels of dgs_emd_auction).  The first three kernels share their shape and nothing else: each keeps its own
+// statement of the query state and of its commit (a packed minimum, a packed minimum, an integer sum); the auction's bidding pass
+// keeps a top-2 and is described with its kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -149,8 +150,95 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_search_kernel(long long n_que
     }
 }
 
+// ---- winding number -------------------------------------------------------------------------------------------------------------
+// The shape of tri_search_kernel with a sum where that one has a minimum (dgs_winding_sum; include/dgs_mesh_ops.h states the
+// quantity, dgs_amd/mesh_metrics.py: winding_sums_torch is the same statement in PyTorch).  A workgroup owns WIND_Q = 256 x WIND_K
+// queries (each thread WIND_K of them in registers: coordinates and one 64-bit integer accumulator) and one slice of the table,
+// which it walks in rounds of WIND_T rows.  A round is a straight copy of WIND_T x 48 bytes into LDS; the inner loop reads one row
+// with three 16-byte LDS reads at an address every lane shares -- a broadcast -- and evaluates it for the thread's WIND_K queries.
+// Per pair the half solid angle is turned into the integer rint(theta * 2^28) before it is added: integer addition has no order, so
+// the rounds of a slice, the slices (one 64-bit atomic add per query and slice) and the PyTorch statement all give the same bits.
+// Per pair: 9 subtractions, six dot products, three IEEE square roots, the 8 operations of the denominator, one IEEE division, 14
+// operations of the Horner scheme and about 20 of reflections, guards and the conversion -- the ISA count is in DESIGN section 22;
+// the LDS sees three instructions per WIND_K pairs and is idle.
+// Sizing: 256 rows are 12 KB of LDS, which never limits; the registers do (DESIGN section 22 records the count the compiler
+// reports).  The kernel is bound by VALU issue, four independent pairs per thread give the scheduler its parallelism, so
+// occupancy beyond two waves per SIMD buys nothing.  WIND_CHUNK = 1024 rows per slice: a small mesh still spreads over the
+// device (10^5 queries x 5000 faces are 490 workgroups), a workgroup still evaluates 2^20 pairs per 1024 atomics.
+constexpr int WIND_THREADS = 256, WIND_K = 4, WIND_Q = WIND_THREADS * WIND_K, WIND_T = 256, WIND_ROW = 12, WIND_ROW4 = WIND_ROW / 4, WIND_CHUNK = 1024;
+constexpr float WIND_PI = 3.1415927410125732f, WIND_HALF_PI = 1.5707963705062866f;   // the fp32 neighbours of pi and pi / 2
+constexpr float WIND_SCALE = 268435456.0f;                                            // 2^28: the fixed point of a term
+// atan(r) = r * (c0 + c1 s + ... + c7 s^7), s = r * r, on [0, 1]; c0 is exactly 1 (include/dgs_mesh_ops.h says why)
+constexpr float WIND_C0 = 1.0f, WIND_C1 = -0.3333165943622589f, WIND_C2 = 0.19962704181671143f, WIND_C3 = -0.13976581394672394f,
+                WIND_C4 = 0.09794232249259949f, WIND_C5 = -0.05777356028556824f, WIND_C6 = 0.02304011397063732f,
+                WIND_C7 = -0.004355399403721094f;
+
+// atan2(y, x) of include/dgs_mesh_ops.h: 0 unless both are finite and one is not zero
+__device__ __forceinline__ float wind_atan2(float y, float x) {
+    const float ay = fabsf(y), ax = fabsf(x);
+    const float mx = fmaxf(ay, ax), mn = fminf(ay, ax);
+    const float r = mx > 0.0f ? mn / mx : 0.0f;                           // the IEEE division
+    const float s = r * r;
+    float p = WIND_C7;
+    p = p * s + WIND_C6, p = p * s + WIND_C5, p = p * s + WIND_C4, p = p * s + WIND_C3;
+    p = p * s + WIND_C2, p = p * s + WIND_C1, p = p * s + WIND_C0;
+    p = p * r;
+    p = ay > ax ? WIND_HALF_PI - p : p;
+    p = x < 0.0f ? WIND_PI - p : p;
+    p = y < 0.0f ? -p : p;
+    const bool ok = (ay < __builtin_inff()) & (ax < __builtin_inff()) & (mx > 0.0f);   // false for a NaN
+    return ok ? p : 0.0f;
+}
+
+__global__ __launch_bounds__(WIND_THREADS) void winding_sum_kernel(long long n_query, const float* __restrict__ query, long long n_tri,
+                                                                   const float4* __restrict__ table, long long tri_chunk,
+                                                                   unsigned long long* __restrict__ sums) {
+    __shared__ float4 rows[WIND_T * WIND_ROW4];
+    const long long q0 = (long long)blockIdx.x * WIND_Q + threadIdx.x;     // this thread's queries: q0 + k * WIND_THREADS
+    const long long f_begin = (long long)blockIdx.y * tri_chunk;           // the host clamps tri_chunk to n_tri: no overflow
+    const long long f_end = f_begin + tri_chunk < n_tri ? f_begin + tri_chunk : n_tri;
+    float qx[WIND_K], qy[WIND_K], qz[WIND_K];
+    long long acc[WIND_K];
+#pragma unroll
+    for (int k = 0; k < WIND_K; ++k) {
+        const long long q = q0 + (long long)k * WIND_THREADS;
+        const bool live = q < n_query;                                     // a thread past the end computes on zeros and stores nothing
+        qx[k] = live ? query[3 * q] : 0.0f, qy[k] = live ? query[3 * q + 1] : 0.0f, qz[k] = live ? query[3 * q + 2] : 0.0f;
+        acc[k] = 0;
+    }
+    for (long long fs = f_begin; fs < f_end; fs += WIND_T) {
+        const int n = (int)(f_end - fs < WIND_T ? f_end - fs : WIND_T);   // rows of this round: only they are staged and read
+        __syncthreads();                                                   // the previous round's readers are done
+        const float4* src = table + fs * WIND_ROW4;
+        for (int e = threadIdx.x; e < n * WIND_ROW4; e += WIND_THREADS)    // (fs + n) rows <= n_tri rows: inside the table;
+            rows[e] = src[e];                                              // e < WIND_T * WIND_ROW4: inside the LDS array
+        __syncthreads();
+        for (int j = 0; j < n; ++j) {
+            const float4 r0 = rows[j * WIND_ROW4], r1 = rows[j * WIND_ROW4 + 1], r2 = rows[j * WIND_ROW4 + 2];
+            // A = r0.xyz, B = (r0.w, r1.x, r1.y), C = (r1.z, r1.w, r2.x), n = r2.yzw
+#pragma unroll
+            for (int k = 0; k < WIND_K; ++k) {
+                const float ax = r0.x - qx[k], ay = r0.y - qy[k], az = r0.z - qz[k];
+                const float bx = r0.w - qx[k], by = r1.x - qy[k], bz = r1.y - qz[k];
+                const float cx = r1.z - qx[k], cy = r1.w - qy[k], cz = r2.x - qz[k];
+                const float la = sqrtf(dot3(ax, ay, az, ax, ay, az)), lb = sqrtf(dot3(bx, by, bz, bx, by, bz)),
+                            lc = sqrtf(dot3(cx, cy, cz, cx, cy, cz));      // (the IEEE sqrt)
+                const float num = dot3(ax, ay, az, r2.y, r2.z, r2.w);
+                const float ab = dot3(ax, ay, az, bx, by, bz), bc = dot3(bx, by, bz, cx, cy, cz), ca = dot3(cx, cy, cz, ax, ay, az);
+                const float den = ((la * lb) * lc + ab * lc) + (bc * la + ca * lb);
+                acc[k] += (long long)(int)rintf(wind_atan2(num, den) * WIND_SCALE);   // |theta| <= pi: the term is below 2^30
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < WIND_K; ++k) {
+        const long long q = q0 + (long long)k * WIND_THREADS;
+        if (q < n_query) atomicAdd(&sums[q], (unsigned long long)acc[k]);  // two's complement carries the sign
+    }
+}
+
 // ---- earth mover's distance: the auction ------------------------------------------------------------------------------------------
-// The third all-pairs search (dgs_emd_auction; include/dgs_mesh_ops.h states the quantity and the schedule, dgs_amd/mesh_metrics.py:
+// The fourth all-pairs search (dgs_emd_auction; include/dgs_mesh_ops.h states the quantity and the schedule, dgs_amd/mesh_metrics.py:
 // emd_torch is the same statement in PyTorch).  Per unassigned person i, over ALL objects j: the smallest and the second smallest
 // w = c_ij + p_j and the lowest j of the smallest -- a top-2 where nn_search_kernel keeps a top-1, with an integer price per point.
 // Everything the auction iterates on is an integer: c_ij is an int in [0, 2^20], prices, bids and w are 64-bit.

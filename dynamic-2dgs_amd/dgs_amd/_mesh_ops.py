@@ -1,5 +1,5 @@
 """ctypes binding of libdgs_mesh_ops.so (include/dgs_mesh_ops.h): TSDF fusion, marching tetrahedra, the all-pairs nearest-neighbour
-and closest-triangle searches, the auction solver of the earth mover's distance, the z-buffer triangle rasterizer, the connected components, the
+and closest-triangle searches, the winding-number sums, the auction solver of the earth mover's distance, the z-buffer triangle rasterizer, the connected components, the
 quadric vertex clustering, the smoothing steps, the edge collapse rounds and the hole filling for gfx950, used by dgs_amd.mesh,
 dgs_amd.mesh_metrics, dgs_amd.mesh_render, dgs_amd.mesh_clean, dgs_amd.mesh_simplify, dgs_amd.mesh_smooth, dgs_amd.mesh_decimate and
 dgs_amd.mesh_fill when the data lives on a HIP device.  CPU tensors use the PyTorch / NumPy statements in those modules."""
@@ -27,11 +27,13 @@ _SIGNATURES = {
     "dgs_tsdf_integrate": (_ci, [_ci, _ci, _ci, _cf, _cf, _cf, _cf, _ci, _ci, _ci, _vp, _vp, _vp, _cf, _cf, _cf, _ci, _vp, _vp, _vp, _vp]),
     "dgs_mt_classify": (_ci, [_ci, _ci, _ci] + [_vp] * 6),
     "dgs_mt_emit": (_ci, [_ci, _ci, _ci, _cf, _cf, _cf, _cf, _vp, _vp, _ll, _vp, _vp, _vp, _ll] + [_vp] * 7),
-    # the two searches (mesh_search_kernels.h)
+    # the two searches and the winding sums (mesh_search_kernels.h)
     "dgs_nn_search": (_ci, _SEARCH),
     "dgs_nn_layout": (_ci, _LAYOUT),
     "dgs_tri_search": (_ci, _SEARCH),
     "dgs_tri_layout": (_ci, _LAYOUT),
+    "dgs_winding_sum": (_ci, _SEARCH),
+    "dgs_winding_layout": (_ci, _LAYOUT),
     # earth mover's distance (its kernels close mesh_search_kernels.h)
     "dgs_emd_auction": (_ci, [_ll, _vp, _vp, _cf, _ll, _vp, _ll, _vp, _vp, _vp, _vp]),
     "dgs_emd_layout": (_ci, _LAYOUT),
@@ -162,7 +164,7 @@ def marching_tetrahedra(dims, origin, voxel, tsdf, weight, color=None):
     return vertices, faces, colors
 
 
-# ---- the two searches and the earth mover's distance ----------------------------------------------------------------------------
+# ---- the searches, the winding sums and the earth mover's distance ----------------------------------------------------------------------------
 def _search(who, entry, layout, chunk, query, qname, ref, rname, cols, expected):
     """nearest and closest_face: device and dtype checks, the chunk default (layout[2]), the `best` buffer, the call and the
     unpacking of the packed minimum."""
@@ -201,6 +203,26 @@ def closest_face(points, table, tri_chunk=None):
     layout = tri_layout()
     return _search("closest_face", "dgs_tri_search", layout, tri_chunk, points, "points", table, "table", layout[3],
                    "points [Nq,3] and table [Nf,%d]" % layout[3])
+
+
+def winding_layout():
+    """(queries per workgroup, triangles per LDS round, default tri_chunk, floats per table row) of dgs_winding_sum."""
+    return _layout("dgs_winding_layout", 4)
+
+
+def winding_sums(points, table, tri_chunk=None):
+    """dgs_winding_sum: sums [Nq] int64, the fixed-point winding sums of table [Nf,row] (mesh_metrics.winding_table) at every point
+    of points [Nq,3]; W = sums / (2 pi 2^28).  The result does not depend on tri_chunk (default: winding_layout()[2], raised where
+    that would make more than 65535 slices)."""
+    who, layout, dev = "winding_sums", winding_layout(), points.device
+    _tensor(points, _f32, None, who + ": points"), _tensor(table, _f32, None, who + ": table")
+    _same_device(who, "points", dev, table)
+    if points.dim() != 2 or points.shape[1] != 3 or table.dim() != 2 or table.shape[1] != layout[3]:
+        raise RuntimeError("%s: points [Nq,3] and table [Nf,%d] are expected" % (who, layout[3]))
+    chunk = max(layout[2], -(-table.shape[0] // 65535)) if tri_chunk is None else int(tri_chunk)
+    sums = torch.empty(points.shape[0], dtype=_i64, device=dev)
+    _call(dev, "dgs_winding_sum", points.shape[0], points.data_ptr(), table.shape[0], table.data_ptr(), chunk, sums.data_ptr())
+    return sums
 
 
 def emd_layout():

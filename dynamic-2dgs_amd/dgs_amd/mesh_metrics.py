@@ -8,10 +8,14 @@ mode="surface" a sample's distance is the exact one to the other SURFACE (the mi
                    arithmetic and the tie rule); CPU tensors: nearest_torch, the PyTorch statement of the same arithmetic
   closest_face     exact point-to-triangle distance to the closest face of a mesh; HIP device: dgs_tri_search over the rows of
                    triangle_table; CPU tensors: closest_face_torch, the PyTorch statement of the same arithmetic
+  winding_number   generalised winding number of a mesh at query points (1 inside, 0 outside, smooth near an open rim); HIP device:
+                   dgs_winding_sum over the rows of winding_table; CPU tensors: winding_sums_torch, the same arithmetic -- the sums
+                   are integers and bit-identical between the two; contains, signed_distance, mesh_volume, is_outward and
+                   volume_iou are built on it
   emd              earth mover's distance of two equal-sized point sets: a one-to-one matching by an integer auction; HIP device:
                    dgs_emd_auction; CPU tensors: emd_torch, the PyTorch statement of the same schedule (bit-identical)
   sample_surface   area-weighted uniform samples of a mesh, the same points on every device
-  mesh_distance    the metrics of one pair of meshes
+  mesh_distance    the metrics of one pair of meshes (iou_samples > 0: with volume_iou)
   read_mesh        .ply (io.read_mesh_ply) or .obj (io.read_mesh_obj)
   evaluate_meshes  frame_<i>.ply of a directory against the i-th ground-truth mesh of another -> mesh_metrics.json
 
@@ -178,6 +182,197 @@ def closest_face(points, vertices, faces, face_chunk=None):
     return _mesh_ops.closest_face(points.float().contiguous(), triangle_table(vertices.float(), faces), face_chunk)
 
 
+# ---- winding number -------------------------------------------------------------------------------------------------------------
+WIND_ROW = 12                      # floats of a winding_table row (= dgs_winding_layout()[3])
+WIND_SCALE = float(1 << 28)        # a pair's half solid angle enters the sum as rint(theta * 2^28)
+# W = sum * WIND_UNIT in float64: one correctly rounded multiplication on any device (a division by a Python scalar is not one
+# everywhere: a device may multiply by the reciprocal), so equal sums give equal W
+WIND_UNIT = 1.0 / (2.0 * math.pi * WIND_SCALE)
+_WIND_LIVE = 32                    # winding_sums_torch keeps about thirty [chunk, Nf] intermediates alive, float64 ones among them
+_WIND_PI, _WIND_HALF_PI = 3.1415927410125732, 1.5707963705062866     # the fp32 values nearest to pi and pi / 2
+# atan(r) = r (c0 + c1 s + ... + c7 s^7), s = r r, on [0, 1]: fp32 values, c0 pinned to 1 (include/dgs_mesh_ops.h says why)
+_WIND_ATAN = (1.0, -0.3333165943622589, 0.19962704181671143, -0.13976581394672394, 0.09794232249259949, -0.05777356028556824,
+              0.02304011397063732, -0.004355399403721094)
+
+
+def _faces(faces, who):
+    if not torch.is_tensor(faces) or faces.dim() != 2 or faces.shape[1] != 3 or faces.is_floating_point():
+        raise ValueError("%s: faces must be an integer tensor [Nf,3]" % who)
+    return faces
+
+
+@torch.no_grad()
+def winding_table(vertices, faces):
+    """[Nf', WIND_ROW] fp32 on the device of `vertices`: per face with corners A, B, C the row A, B, C, n = cross(B - A, C - A) --
+    the table of dgs_winding_sum (include/dgs_mesh_ops.h), elementwise fp32 operations, every one rounded on its own.  Faces that
+    name a vertex twice are dropped first (they subtend nothing), so Nf' <= Nf."""
+    v = vertices.detach().reshape(-1, 3).float()
+    f = faces.detach().reshape(-1, 3).long().to(v.device)
+    f = f[(f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 2] != f[:, 0])]
+    xyz = lambda p: (p[:, 0], p[:, 1], p[:, 2])
+    a, b, c = xyz(v[f[:, 0]]), xyz(v[f[:, 1]]), xyz(v[f[:, 2]])
+    sub = lambda p, q: (p[0] - q[0], p[1] - q[1], p[2] - q[2])
+    return torch.stack(a + b + c + _cross(sub(b, a), sub(c, a)), dim=1).contiguous()
+
+
+def _sqrt32(x):
+    """The correctly rounded fp32 square root on any device (the float64 one rounded to fp32: see _emd_costs)."""
+    return torch.sqrt(x.double()).float()
+
+
+def _wind_atan2(y, x):
+    """ATAN2 of include/dgs_mesh_ops.h on fp32 tensors, one rounding per operation; the division is the float64 one rounded to fp32,
+    which is the correctly rounded fp32 quotient (53 >= 2 * 24 + 2 bits) whatever the device's own fp32 division does."""
+    ay, ax = y.abs(), x.abs()
+    mx, mn = torch.maximum(ay, ax), torch.minimum(ay, ax)
+    r = torch.where(mx > 0, (mn.double() / mx.double()).float(), torch.zeros_like(mx))
+    s = r * r
+    p = torch.full_like(s, _WIND_ATAN[7])
+    for c in _WIND_ATAN[6::-1]:
+        p = p * s + c
+    p = p * r
+    p = torch.where(ay > ax, _WIND_HALF_PI - p, p)
+    p = torch.where(x < 0, _WIND_PI - p, p)
+    p = torch.where(y < 0, -p, p)
+    return torch.where(torch.isfinite(y) & torch.isfinite(x) & (mx > 0), p, torch.zeros_like(p))
+
+
+def _pair_terms(points, col):
+    """[Nq, Nf] int64: rint(theta * 2^28) of every (point, row) pair; col = the table's columns as [12, 1, Nf]."""
+    q = (points[:, 0:1], points[:, 1:2], points[:, 2:3])
+    a, b, c = ((col[3 * k] - q[0], col[3 * k + 1] - q[1], col[3 * k + 2] - q[2]) for k in range(3))
+    la, lb, lc = _sqrt32(_dot(a, a)), _sqrt32(_dot(b, b)), _sqrt32(_dot(c, c))
+    num = _dot(a, (col[9], col[10], col[11]))
+    den = ((la * lb) * lc + _dot(a, b) * lc) + (_dot(b, c) * la + _dot(c, a) * lb)
+    return torch.round(_wind_atan2(num, den) * WIND_SCALE).to(torch.int64)
+
+
+@torch.no_grad()
+def winding_sums_torch(points, table, chunk=None):
+    """The arithmetic of dgs_winding_sum in PyTorch, in fp32 on the device of the tensors: per pair a = A - q, b, c likewise, their
+    norms by the correctly rounded sqrt, num = dot(a, n), den = ((la lb) lc + dot(a, b) lc) + (dot(b, c) la + dot(c, a) lb),
+    theta = ATAN2(num, den) (_wind_atan2), term = rint(theta 2^28) as int64; then the integer sum over the faces.  chunk: faces per
+    partial sum (None: all at once) -- integer addition has no order, so the result does not depend on it, nor on the order of the
+    rows.  -> sums [Nq] int64.  The CPU path, the comparator of the GPU tests and the baseline of tools/mesh_winding_timing.py."""
+    nq, nf = points.shape[0], table.shape[0]
+    if nf < 1:
+        raise ValueError("winding_number: the mesh has no faces")
+    points, table = points.float(), table.float()
+    chunk = nf if chunk is None else max(1, int(chunk))
+    step = max(1, _PAIR_BUDGET // _WIND_LIVE // min(chunk, nf))
+    sums = torch.zeros(nq, dtype=torch.int64, device=points.device)
+    for fs in range(0, nf, chunk):
+        col = table[fs:fs + chunk].t().contiguous().unsqueeze(1)            # [12, 1, n]: col[i] broadcasts against [step, 1]
+        for s in range(0, nq, step):
+            sums[s:s + step] += _pair_terms(points[s:s + step], col).sum(dim=1)
+    return sums
+
+
+def _winding_args(points, vertices, faces, who):
+    """Shapes, devices and face indices; the coordinates may be anything -- a non-finite pair adds 0 to the sum."""
+    for x, what in ((points, "points"), (vertices, "vertices")):
+        if not torch.is_tensor(x) or x.dim() != 2 or x.shape[1] != 3 or not x.is_floating_point():
+            raise ValueError("%s: %s must be a floating-point tensor [N,3]" % (who, what))
+    _faces(faces, who)
+    if faces.shape[0] < 1:
+        raise ValueError("%s: the mesh has no faces" % who)
+    if points.device != vertices.device or points.device != faces.device:
+        raise ValueError("%s: points, vertices and faces live on different devices" % who)
+    if int(faces.min()) < 0 or int(faces.max()) >= vertices.shape[0]:
+        raise ValueError("%s: a face names a vertex outside [0, %d)" % (who, vertices.shape[0]))
+
+
+@torch.no_grad()
+def winding_sums(points, vertices, faces, face_chunk=None):
+    """sums [Nq] int64 of dgs_winding_sum for the mesh at the points, in fp32: HIP tensors use the kernel (a missing library is an
+    error), CPU tensors winding_sums_torch; the two give the same integers."""
+    _winding_args(points, vertices, faces, "winding_number")
+    table = winding_table(vertices, faces)
+    if table.shape[0] < 1:
+        raise ValueError("winding_number: every face of the mesh names a vertex twice")
+    if points.device.type == "cpu":
+        return winding_sums_torch(points, table, face_chunk)
+    from . import _mesh_ops
+    return _mesh_ops.winding_sums(points.float().contiguous(), table, face_chunk)
+
+
+def winding_number(points, vertices, faces, face_chunk=None):
+    """W [Nq] float64: the generalised winding number of the mesh (vertices [Nv,3], faces [Nf,3]) at every point of points [Nq,3]:
+    the signed solid angle the faces subtend, over 4 pi.  1 inside a closed mesh wound outward, 0 outside, -1 inside one wound
+    inward, k inside k nested shells; near an open rim a smooth value in between, which is why it -- not a ray's parity -- is the
+    inside test for extracted frames and unwelded ground truth.  A point ON the surface has no answer (about 1/2 on a smooth
+    patch).  Brute force over all (point, face) pairs, fp32 per pair, summed as integers: W = winding_sums * WIND_UNIT (1 / (2 pi 2^28)), identical on
+    every device and for every face order.  face_chunk: the kernel's slice of the faces per workgroup, the statement's faces per
+    partial sum; the result does not depend on it.  Non-finite points or vertices are legal: their pairs add 0.  Nf = 0, bad
+    shapes, face indices out of range and mixed devices raise ValueError before anything is launched."""
+    return winding_sums(points, vertices, faces, face_chunk).double() * WIND_UNIT
+
+
+def contains(points, vertices, faces, threshold=0.5):
+    """bool [Nq]: winding_number > threshold.  For a closed mesh wound outward this is "inside"; a mesh wound inward contains
+    nothing (its W is -1 inside: is_outward tells)."""
+    return winding_number(points, vertices, faces) > threshold
+
+
+def signed_distance(points, vertices, faces):
+    """[Nq]: the distance of closest_face with a sign, -sqrt(d2) where `contains` says inside and +sqrt(d2) outside; the dtype is
+    closest_face's (fp32 on a HIP device).  Finite coordinates only, as for closest_face."""
+    d2, _ = closest_face(points, vertices, faces)
+    d = d2.sqrt()
+    return torch.where(contains(points, vertices, faces), -d, d)
+
+
+@torch.no_grad()
+def mesh_volume(vertices, faces):
+    """The signed volume the mesh encloses, a Python float: the divergence sum over the faces of A . (B x C) / 6 in float64.
+    Positive for a closed mesh wound outward; for an open mesh it depends on the origin and means little."""
+    v = vertices.detach().reshape(-1, 3).double()
+    f = _faces(faces, "mesh_volume").long().to(v.device)
+    a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    return float((a * torch.cross(b, c, dim=1)).sum() / 6.0)
+
+
+def is_outward(vertices, faces):
+    """mesh_volume(vertices, faces) > 0: the faces of a closed mesh are wound counter-clockwise seen from outside, which is what
+    makes winding_number +1 inside.  No more than that sign: an open or self-intersecting mesh gets an answer too."""
+    return mesh_volume(vertices, faces) > 0.0
+
+
+def _volume_iou(pv, pf, gv, gf, n_samples, seed):
+    """volume_iou on mesh tensors that share a device."""
+    n = int(n_samples)
+    if n < 1:
+        raise ValueError("volume_iou: n_samples must be >= 1")
+    lo = torch.minimum(pv.min(0).values, gv.min(0).values).double().cpu()     # the six extrema are exact on any device; the
+    hi = torch.maximum(pv.max(0).values, gv.max(0).values).double().cpu()     # arithmetic on them runs on the CPU
+    u = torch.rand((n, 3), dtype=torch.float64, generator=torch.Generator().manual_seed(int(seed)))
+    pts = (lo + u * (hi - lo)).float().to(pv.device)
+    in_p, in_g = contains(pts, pv, pf), contains(pts, gv, gf)
+    n_p, n_g, n_i, n_u = int(in_p.sum()), int(in_g.sum()), int((in_p & in_g).sum()), int((in_p | in_g).sum())
+    box = float((hi - lo).prod())
+    return {"iou": n_i / n_u if n_u else 0.0, "volume_pred": box * n_p / n, "volume_gt": box * n_g / n, "volume_intersection": box * n_i / n,
+            "iou_samples": n}
+
+
+@torch.no_grad()
+def volume_iou(pred, gt, n_samples=100_000, seed=0, device="cuda:0", gt_transform=None):
+    """Volumetric intersection over union of two meshes, each a (vertices, faces) pair of arrays or tensors, by Monte Carlo:
+    n_samples points uniform in the joint bounding box of the two meshes -- [n,3] float64 uniforms from a CPU
+    torch.Generator().manual_seed(seed), scaled into the box in float64 on the CPU, then cast to fp32, so every device tests the same
+    points -- and `contains` against both meshes on `device`.  gt_transform: as in mesh_distance.
+      iou                  samples inside both / samples inside either; 0 when no sample is inside either
+      volume_pred, volume_gt, volume_intersection    box volume x the share of the samples inside
+      iou_samples          n_samples
+    The samples and the winding sums are the same on every device, so are the returned floats.  The standard deviation of a share p
+    is sqrt(p (1 - p) / n); meshes must be wound outward (is_outward) to contain anything."""
+    dev = torch.device(device)
+    pv, pf = _mesh_tensors(pred, dev)
+    gv, gf = _mesh_tensors(gt, dev)
+    if gt_transform is not None:
+        gv = _transformed(gv, gt_transform)
+    return _volume_iou(pv, pf, gv, gf, n_samples, seed)
+
+
 # ---- earth mover's distance -------------------------------------------------------------------------------------------------------
 EMD_COST_CAP = 1 << 20     # costs are integers in [0, 2^20]: the bounding-box diagonal of both sets is 2^20 quanta
 EMD_BIDDER_BITS, EMD_BID_BITS = 24, 39   # the packed word of an object: bid << 24 | bidder, below 2^63 (signed = unsigned order)
@@ -318,6 +513,12 @@ def _mesh_tensors(mesh, device):
     return v.reshape(-1, 3), f.reshape(-1, 3).long()
 
 
+def _transformed(vertices, transform):
+    """x' = M[:3,:3] x + M[:3,3] of the [4,4] transform (column-vector convention), in float64, back in the dtype of the vertices."""
+    m = torch.as_tensor(np.asarray(transform, dtype=np.float64), device=vertices.device)
+    return (vertices.double() @ m[:3, :3].T + m[:3, 3]).to(vertices.dtype)
+
+
 @torch.no_grad()
 def sample_surface(vertices, faces, n, seed):
     """n points uniform over the surface of the mesh -> (points [n,3] f32, face_ids [n] int64, normals [n,3] f32 -- the unit normal
@@ -376,7 +577,7 @@ def _surface_hits(points, vertices, faces):
 
 @torch.no_grad()
 def mesh_distance(pred, gt, n_samples=100_000, seed=0, thresholds=(0.005, 0.01, 0.02), device="cuda:0", gt_transform=None, mode="samples",
-                  emd_samples=0):
+                  emd_samples=0, iou_samples=0):
     """Metrics between the surfaces of pred and gt, each a (vertices [Nv,3], faces [Nf,3]) pair of arrays or tensors.  n_samples
     points are drawn on pred with `seed` and on gt with `seed + 1` (sample_surface), then `nearest` runs both ways on `device`.
     gt_transform: optional [4,4] (column-vector convention, x' = M[:3,:3] x + M[:3,3]) applied to the ground-truth vertices first.
@@ -397,6 +598,8 @@ def mesh_distance(pred, gt, n_samples=100_000, seed=0, thresholds=(0.005, 0.01, 
       emd, emd_gap, emd_samples, emd_rounds   only with emd_samples > 0: `emd` of the first emd_samples pred samples against the
                           first emd_samples gt samples (the samples are independent draws, so a prefix is a uniform sample too); at
                           most n_samples.  A one-to-one matching: a dense blob near the surface, cheap for the Chamfer distance, is not.
+      iou, volume_pred, volume_gt, volume_intersection, iou_samples   only with iou_samples > 0: `volume_iou` of the two meshes with
+                          iou_samples points and `seed` -- the one score here that asks whether the meshes enclose the same volume.
     The per-threshold entries are dicts keyed by '%g' % tau.  Sample-to-sample distances carry the sampling floor: a surface against
     itself measures about 0.5 sqrt(area / n_samples) per direction, not 0; sample-to-surface distances (mode "surface") measure 0."""
     if mode not in ("samples", "surface"):
@@ -404,12 +607,14 @@ def mesh_distance(pred, gt, n_samples=100_000, seed=0, thresholds=(0.005, 0.01, 
     emd_samples = int(emd_samples)
     if emd_samples < 0 or emd_samples > int(n_samples):
         raise ValueError("mesh_distance: emd_samples must be in [0, n_samples = %d], not %d" % (int(n_samples), emd_samples))
+    iou_samples = int(iou_samples)
+    if iou_samples < 0:
+        raise ValueError("mesh_distance: iou_samples must be >= 0, not %d" % iou_samples)
     dev = torch.device(device)
     pv, pf = _mesh_tensors(pred, dev)
     gv, gf = _mesh_tensors(gt, dev)
     if gt_transform is not None:
-        m = torch.as_tensor(np.asarray(gt_transform, dtype=np.float64), device=dev)
-        gv = (gv.double() @ m[:3, :3].T + m[:3, 3]).to(gv.dtype)
+        gv = _transformed(gv, gt_transform)
     pp, _, pn = sample_surface(pv, pf, n_samples, seed)
     gp, _, gn = sample_surface(gv, gf, n_samples, seed + 1)
     if mode == "samples":
@@ -436,6 +641,8 @@ def mesh_distance(pred, gt, n_samples=100_000, seed=0, thresholds=(0.005, 0.01, 
     if emd_samples > 0:
         m = emd(pp[:emd_samples], gp[:emd_samples])
         out.update({k: m[k] for k in ("emd", "emd_gap", "emd_samples", "emd_rounds")})
+    if iou_samples > 0:
+        out.update(_volume_iou(pv, pf, gv, gf, iou_samples, seed))
     return out
 
 
@@ -468,7 +675,7 @@ def _flat(m):
 
 
 def evaluate_meshes(pred_dir, gt_dir, n_samples=100_000, seed=0, thresholds=(0.005, 0.01, 0.02), device="cuda:0", gt_transform=None, log=None,
-                    mode="samples", clean_gt=False, emd_samples=0):
+                    mode="samples", clean_gt=False, emd_samples=0, iou_samples=0):
     """frame_<i>.ply of pred_dir against the i-th ground-truth mesh of gt_dir (its .obj / .ply files in natural sort order), for
     every i.  A different number of frames and ground-truth meshes is an error.  Writes <pred_dir>/mesh_metrics.json:
     {"frames": [{"frame": i, "pred": ..., "gt": ..., <metrics>}], "mean": {<metric>: mean over the frames}, "settings": ...} with
@@ -476,7 +683,9 @@ def evaluate_meshes(pred_dir, gt_dir, n_samples=100_000, seed=0, thresholds=(0.0
     clean_gt: weld and clean every ground-truth mesh on load (mesh_clean.clean_mesh on `device`: an OBJ whose faces each carry their
     own three vertices becomes an indexed mesh again, duplicated and degenerate triangles go); recorded under "settings" when set.
     emd_samples: as in mesh_distance (0: no earth mover's distance, the result is what it was without the argument); the four emd
-    keys then appear per frame and in "mean", and the value is recorded under "settings" when set."""
+    keys then appear per frame and in "mean", and the value is recorded under "settings" when set.
+    iou_samples: as in mesh_distance, under the same rule: 0 changes nothing, otherwise the five volume keys appear per frame and in
+    "mean" and the value is recorded under "settings"."""
     def load_gt(path):
         v, f = read_mesh(path)
         if not clean_gt:
@@ -499,7 +708,8 @@ def evaluate_meshes(pred_dir, gt_dir, n_samples=100_000, seed=0, thresholds=(0.0
     rows = []
     for i in range(len(gts)):
         m = _flat(mesh_distance(read_mesh(os.path.join(pred_dir, frames[i])), load_gt(os.path.join(gt_dir, gts[i])), n_samples=n_samples,
-                                seed=seed, thresholds=thresholds, device=device, gt_transform=gt_transform, mode=mode, emd_samples=emd_samples))
+                                seed=seed, thresholds=thresholds, device=device, gt_transform=gt_transform, mode=mode, emd_samples=emd_samples,
+                                iou_samples=iou_samples))
         rows.append(dict({"frame": i, "pred": frames[i], "gt": gts[i]}, **m))
         if log is not None:
             log("frame %d (%s vs %s): chamfer %.6f, accuracy %.6f, completeness %.6f, normal consistency %.4f"
@@ -512,12 +722,14 @@ def evaluate_meshes(pred_dir, gt_dir, n_samples=100_000, seed=0, thresholds=(0.0
         result["settings"]["clean_gt"] = True
     if emd_samples:
         result["settings"]["emd_samples"] = int(emd_samples)
+    if iou_samples:
+        result["settings"]["iou_samples"] = int(iou_samples)
     with open(os.path.join(pred_dir, "mesh_metrics.json"), "w") as fh:
         json.dump(result, fh, indent=1)
     return result
 
 
-def main(argv=None):
+def _parser():
     import argparse
     ap = argparse.ArgumentParser(prog="python -m dgs_amd.mesh_metrics",
                                  description="Chamfer distance, F-score and normal consistency of frame_<i>.ply against ground-truth meshes.")
@@ -532,9 +744,15 @@ def main(argv=None):
     ap.add_argument("--clean-gt", action="store_true", help="weld and clean the ground-truth meshes on load (dgs_amd.mesh_clean.clean_mesh)")
     ap.add_argument("--emd", type=int, default=0, metavar="N",
                     help="also the earth mover's distance of the first N samples of each mesh (one-to-one matching, dgs_amd.mesh_metrics.emd)")
-    a = ap.parse_args(argv)
+    ap.add_argument("--iou", type=int, default=0, metavar="N",
+                    help="also the volumetric IoU from N points in the joint bounding box (winding numbers, dgs_amd.mesh_metrics.volume_iou)")
+    return ap
+
+
+def main(argv=None):
+    a = _parser().parse_args(argv)
     return evaluate_meshes(a.pred_dir, a.gt_dir, n_samples=a.samples, seed=a.seed, thresholds=tuple(a.thresholds), device=a.device, log=print,
-                           mode=a.mode, clean_gt=a.clean_gt, emd_samples=a.emd)
+                           mode=a.mode, clean_gt=a.clean_gt, emd_samples=a.emd, iou_samples=a.iou)
 
 
 if __name__ == "__main__":

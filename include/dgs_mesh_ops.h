@@ -135,6 +135,54 @@ int dgs_tri_search(long long n_query, const float* query, long long n_tri, const
 /* out = {queries per workgroup, triangles per LDS round, default tri_chunk, floats per table row}. */
 int dgs_tri_layout(int out[4]);
 
+/* Generalised winding number of a triangle mesh at every query point (brute force, all pairs): 1 inside a closed, outward-wound
+ * mesh, 0 outside, -1 inside an inward-wound one, and a smooth value in between near an open rim -- the inside / outside test
+ * behind contains, signed_distance and volume_iou of dgs_amd/mesh_metrics.py.  Version 2 libraries from this commit on also carry
+ * the dgs_winding_* pair; the version number is unchanged because nothing that existed before changes (the precedent of dgs_tri_*).
+ * For every query q
+ *   sums[q] = sum over f in [0, n_tri) of (long long) rint(theta(q, f) * 2^28),      W(q) = sums[q] / (2 pi 2^28)
+ * with theta half the signed solid angle of face f seen from q (van Oosterom and Strackee).  W is formed by the caller in float64, as one multiplication by 1 / (2 pi 2^28).
+ *
+ * THE TABLE.  One row of 12 fp32 values per triangle = 48 bytes, computed once outside the kernel (dgs_amd/mesh_metrics.py:
+ * winding_table, elementwise PyTorch):  A, B, C, n = cross(B - A, C - A)  (three floats each; dot and cross as for dgs_tri_search,
+ * every operation rounded on its own).  dgs_winding_layout reports the row length.
+ *
+ * THE PAIR.  Every operation a separately rounded fp32 one (-ffp-contract=off; dgs_amd/mesh_metrics.py: winding_sums_torch states
+ * the same arithmetic in PyTorch), square roots and the division the correctly rounded IEEE ones:
+ *   a = A - q, b = B - q, c = C - q;   la = sqrt(dot(a, a)), lb, lc likewise
+ *   num = dot(a, n)             -- equal to the triple product a . (b x c) (b - a and c - a are the edges, whatever q is) without
+ *                                  its cancellation: for a small, far triangle the triple product of three nearly parallel
+ *                                  vectors loses about three digits
+ *   den = ((la * lb) * lc + dot(a, b) * lc) + (dot(b, c) * la + dot(c, a) * lb)
+ *   theta = ATAN2(num, den)
+ * ATAN2(y, x) is written out, not left to a library:
+ *   ay = |y|, ax = |x|;   r = min(ay, ax) / max(ay, ax), 0 where the maximum is 0;   s = r * r
+ *   p = (((((((c7 s + c6) s + c5) s + c4) s + c3) s + c2) s + c1) s + c0) * r          (Horner, one rounding per operation)
+ *     c0 = 1                         c1 = -0.3333165943622589       c2 = 0.19962704181671143      c3 = -0.13976581394672394
+ *     c4 = 0.09794232249259949       c5 = -0.05777356028556824      c6 = 0.02304011397063732      c7 = -0.004355399403721094
+ *   (the fp32 values nearest to these decimals; a minimax fit of atan on [0, 1] with c0 PINNED to 1: most pairs subtend tiny angles,
+ *   where p = c0 r to rounding, so any other c0 is a relative bias of the whole sum -- an unconstrained fit puts every closed mesh at
+ *   W = c0.  The fit's error is 5e-8 rad, 1.3e-7 rad with the roundings of the fp32 evaluation.)
+ *   if ay > ax: p = PI_2 - p;   if x < 0: p = PI - p;   if y < 0: p = -p       (PI_2, PI: the fp32 values nearest to pi / 2 and pi)
+ *   ATAN2 = p if y and x are both finite and not both zero, else 0 (a zero of either sign counts as not negative)
+ * so a query on a vertex (num = den = 0), a NaN or infinite query and a NaN or infinite vertex add 0: every sum is finite.
+ * THE SUM is an integer: theta * 2^28 is exact, rint rounds to nearest even, |term| < 2^30 and n_tri < 2^31 keep |sum| < 2^61.
+ * Integer addition has no order, so the result is bit-identical from run to run, under any permutation or slicing of the faces,
+ * and between the kernel and the PyTorch statement.
+ *   query [n_query,3] fp32;   table [n_tri,12] fp32, 16-byte aligned;   sums [n_query] int64 -- set to zero on `stream` by this call
+ *   tri_chunk: slices of tri_chunk triangles (the last one ragged), one grid row per slice, merged in `sums` by one 64-bit atomic
+ *     add per query and slice (two's complement carries the sign), so the result does not depend on tri_chunk (values above
+ *     n_tri mean one slice; dgs_winding_layout gives the default).
+ * Refused with a negative status before any launch: n_tri < 1, n_tri >= 2^31, n_query < 0, tri_chunk < 1, a null pointer with a
+ * non-zero count, a table that is not 16-byte aligned, more than 65535 slices.  n_query == 0 returns 0 and launches nothing.  A
+ * triangle of the last, ragged round or slice is never read past n_tri.  No kernel waits for another, no trip count is read from
+ * device memory.  Not a fast method: no tree, no multipole expansion, n_query * n_tri pairs. */
+int dgs_winding_sum(long long n_query, const float* query, long long n_tri, const float* table, long long tri_chunk,
+                    long long* sums, void* stream);
+
+/* out = {queries per workgroup, triangles per LDS round, default tri_chunk, floats per table row}. */
+int dgs_winding_layout(int out[4]);
+
 /* Earth mover's distance between two point sets of the same size n: a minimum-cost perfect matching by a synchronous forward
  * auction with eps-scaling on INTEGER costs (dgs_amd/mesh_metrics.py: emd_torch states the same schedule in
  * PyTorch and the two agree bit for bit: assignment, prices, rounds).  Version 2 libraries from this commit on also carry the
