@@ -46,9 +46,9 @@ def run_hip(case, gc=None, go=None, colors_precomp=None, dev="cuda:0", debug=Tru
     return out
 
 
-def run_hip_raw(case, dev="cuda:0"):
+def run_hip_raw(case, dev="cuda:0", planes=True):
     """Calls the extension entry point directly and unpacks the private buffers (layout from
-    dgs_debug_layout)."""
+    dgs_debug_layout).  planes=False leaves out final_T and n_contrib (un-tiling them is seconds of NumPy on a 3088 x 3088 image)."""
     P, H, W = case["means3D"].shape[0], case["image_height"], case["image_width"]
     e = torch.empty(0, device=dev)
     t = lambda k: case[k].to(dev).contiguous()
@@ -76,16 +76,20 @@ def run_hip_raw(case, dev="cuda:0"):
         img[:, :, ly, lx] = a
         return img.transpose(0, 2, 1, 3).reshape(tiles_y * 16, tiles_x * 16)[:H, :W]
 
-    fT = ib[i_off[0]:i_off[0] + 3 * plane * 4].view(np.float32).reshape(3, plane)
-    nc = ib[i_off[1]:i_off[1] + 2 * plane * 4].view(np.uint32).reshape(2, plane)
+    # slots of the forward's dispatch order: tile_order_kernels.h order_slots (tile order 4 leaves empty slots), never fewer than T
+    order_len = max(T, 8 * 16 * ((((tiles_x + 3) // 4) * ((tiles_y + 3) // 4) + 7) // 8 + 1))
     out = dict(
         R=R, color=color.cpu().numpy(), allmap=allmap.cpu().numpy(), radii=radii.cpu().numpy(), rec=rec,
-        final_T=np.stack([untile(fT[i]) for i in range(3)]), n_contrib=np.stack([untile(nc[i]) for i in range(2)]),
+        order_fwd=ib[i_off[4]:i_off[4] + order_len * 4].view(np.uint32), order_slots=order_len,
         ranges=ib[i_off[2]:i_off[2] + T * 8].view(np.uint32).reshape(T, 2),
         tile_last=ib[i_off[3]:i_off[3] + T * 4].view(np.uint32),
         point_list=bb[b_off[0]:b_off[0] + R * 4].view(np.uint32) if R > 0 else np.zeros(0, np.uint32),
         keys=bb[b_off[1]:b_off[1] + R * 8].view(np.uint64) if R > 0 else np.zeros(0, np.uint64),
     )
+    if planes:
+        fT = ib[i_off[0]:i_off[0] + 3 * plane * 4].view(np.float32).reshape(3, plane)
+        nc = ib[i_off[1]:i_off[1] + 2 * plane * 4].view(np.uint32).reshape(2, plane)
+        out.update(final_T=np.stack([untile(fT[i]) for i in range(3)]), n_contrib=np.stack([untile(nc[i]) for i in range(2)]))
     return out
 
 

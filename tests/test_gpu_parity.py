@@ -530,9 +530,12 @@ def test_equal_depths_keep_surfel_index_order(sort_mode, reference_rects):
 
 @pytest.mark.parametrize("sort_mode,P", [(2, 30000), (2, 9000), (1, 30000)])
 def test_long_tile_lists_use_all_sort_paths(sort_mode, P):
-    """Zoomed-in view of big splats: single tiles hold thousands of entries.  P = 30000: 11 k .. 17 k per tile (radix mode:
-    the global-memory fallback above 8192; bitonic mode: the 128 KB LDS network and, above 16384, the fallback); P = 9000:
-    4 k .. 7 k per tile (the 128 KB radix kernel).  The lists must still equal the reference order."""
+    """Zoomed-in view of big splats: single tiles hold thousands of entries.  P = 30000: 11 k .. 17 k per tile, P = 9000: 4 k .. 7 k.
+    Radix mode cuts every list above 2048 entries into segments of 2048 (sort_tiles_radix_kernel<kSegCap, true>) and ranks them
+    against each other (merge_segments_kernel), up to 28 segments = 57 344 entries; only beyond that the global-memory network
+    (sort_tiles_global_kernel) takes over, which these scenes do not reach.  The bitonic modes sort up to 16384 entries in the
+    128 KB LDS network and hand longer lists to the global-memory network.  The lists must still equal the reference order.
+    (tests/test_tile_lists_gpu.py pins the lengths on each of these thresholds.)"""
     from diff_surfel_rasterization import _C
     from gpu_utils import frac_close, img_close, run_hip_raw
     case = small_case(P=P, H=96, W=96, seed=41, view=2, scale_mul=6.0, sh_degree=0, radius=2.2)
